@@ -5,7 +5,7 @@ bench.py -- EM hot-path throughput on MI355X (BASELINE.json metric:
 
     python bench.py [--gpus N] [--steps K] [--warmup W]
                     [--scaling strong|weak] [--total-rows R] [--rows R_PER_GPU]
-                    [--mode rows|restarts] [--restarts B]
+                    [--mode rows|restarts] [--restarts B] [--dump-outputs DIR]
 
 A "step" is one full EM iteration (em.py:57-91 + the convergence bookkeeping
 of em.py:126-143) over this rank's resident rows of the synthetic (synth-v1)
@@ -35,6 +35,14 @@ device from CSR observations by mxm_build_em_matrix; build, linearize and
 posterior pass are timed separately and reported as extra fields).
 
 One JSON line on stdout (rank 0); progress on stderr.
+
+--dump-outputs DIR (rank 0): what the timed path handed its caller, as DIR/<name>.npy in float64, so
+that two builds can be compared output for output (the inputs depend on the arguments alone).  Mode
+rows: the loop vectors right after the last timed step -- props (the proportions), ln_props and
+ln_props_next (the loop's ln_cur / ln_new) and, with one restart, colsum (the M-step column sums,
+all-reduced over the ranks).
+Mode restarts: props, run_props, ln_theta_k, iters and a fixed, seeded sample of rank 0's read_mix
+rows (read_mix_rows holds their indices).  At most DUMP_MAX_BYTES in all.
 """
 
 import argparse
@@ -50,11 +58,27 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_BYTES_PER_S = 8.0e12        # MI355X HBM3E spec (MI355X_MICROARCH.md)
 PARITY_PROPS_BAR = 1e-9              # in-run parity bar on proportions (north-star bar: 1e-6)
+DUMP_MAX_BYTES = 64 << 20            # --dump-outputs: all files together
+DUMP_SAMPLE_ROWS = 512               # --dump-outputs, mode restarts: read_mix rows kept (seeded choice)
 
 
 def log(msg):
     sys.stderr.write("[bench] %s\n" % msg)
     sys.stderr.flush()
+
+
+def dump_outputs(out_dir, arrays):
+    """Write {name: array} as out_dir/<name>.npy in float64 (see --dump-outputs)."""
+    import numpy
+    arrays = {k: numpy.ascontiguousarray(numpy.asarray(v), dtype=numpy.float64) for k, v in arrays.items()}
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_MAX_BYTES:
+        raise SystemExit("bench: --dump-outputs would write %d bytes (limit %d)" % (total, DUMP_MAX_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, arr in sorted(arrays.items()):
+        numpy.save(os.path.join(out_dir, name + ".npy"), arr)
+    log("outputs of the timed path: %s in %s" % (", ".join("%s %s" % (k, arrays[k].shape) for k in sorted(arrays)),
+                                                     out_dir))
 
 
 def parse_args(argv=None):
@@ -98,6 +122,9 @@ def parse_args(argv=None):
     ap.add_argument("--backend", default="nccl",
                     help="torch.distributed backend for N > 1 (nccl = RCCL; gloo only to test the "
                          "multi-process path on a single GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed as DIR/<name>.npy (float64); "
+                         "bench_outputs/ is git-ignored")
     return ap.parse_args(argv)
 
 
@@ -444,6 +471,8 @@ def main(argv=None):
     opts = parse_args(argv)
     if opts.gpus < 1:
         raise SystemExit("bench: --gpus must be >= 1")
+    if opts.steps < 1 or opts.warmup < 0:
+        raise SystemExit("bench: --steps must be >= 1 and --warmup >= 0")
     if opts.gpus > 1 and "RANK" not in os.environ:
         raise SystemExit(spawn_ranks(opts, argv))          # before torch / the GPU are touched
     # stdout carries ONE line, the JSON: libraries that write to file descriptor 1 themselves (RCCL prints a
@@ -690,11 +719,9 @@ def bench_rows(opts, env):
         rank, dist.sharded_em_loop over several): restarts advance in full tiles dealt round-robin, so
         a "step" of B restarts costs B / tile passes over the matrix, not ceil(B / tile)."""
         if use_dist:
-            _, _, sts = mdist.sharded_em_loop(plan, init, 0.0, n_iters, check_every=16,
-                                              exchange=oneshot if oneshot is not None else "rccl")
-        else:
-            _, _, sts = em.em_loop(plan, init, 0.0, n_iters)
-        return sts
+            return mdist.sharded_em_loop(plan, init, 0.0, n_iters, check_every=16,
+                                         exchange=oneshot if oneshot is not None else "rccl")
+        return em.em_loop(plan, init, 0.0, n_iters)
 
     batched = n_runs > 1
     issue_s = None
@@ -703,9 +730,10 @@ def bench_rows(opts, env):
             run_loop(opts.warmup)
         fence()
         t0 = time.perf_counter()
-        loop_states = run_loop(opts.steps)
+        loop_ln_cur, loop_ln_new, loop_states = run_loop(opts.steps)
         fence()
         elapsed = time.perf_counter() - t0
+        outputs = {"props": torch.exp(loop_ln_new), "ln_props": loop_ln_cur, "ln_props_next": loop_ln_new}
     else:
         for _ in range(opts.warmup):
             step()
@@ -716,6 +744,9 @@ def bench_rows(opts, env):
         issue_s = time.perf_counter() - t0           # the host has ENQUEUED every step by now (nothing waited for yet)
         fence()
         elapsed = time.perf_counter() - t0
+        # copies: the sanity pass and the coded leg below reuse these buffers
+        outputs = {"props": props_cur.clone(), "ln_props": ln_cur.clone(), "ln_props_next": ln_new.clone(),
+                   "colsum": colsum.clone()}
     if use_dist:
         tmax = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
@@ -825,6 +856,8 @@ def bench_rows(opts, env):
 
     if rank != 0:
         return None
+    if opts.dump_outputs:
+        dump_outputs(opts.dump_outputs, {k: v.cpu().numpy() for k, v in outputs.items()})
     cells = float(total_rows) * n_haps
     elem = 4.0 if opts.storage == "f32" else 8.0
     algo_bytes = float(n_rows) * n_haps * elem        # this rank's stored matrix is read once per iteration
@@ -966,6 +999,15 @@ def bench_restarts(opts, env):
         sane = sane and float(lse.abs().max().item()) < 1e-9
     if rank != 0:
         return None
+    if opts.dump_outputs:
+        outputs = {"props": res["props"], "run_props": res["run_props"], "ln_theta_k": res["ln_theta_k"],
+                   "iters": numpy.array(iters)}
+        if res["read_mix"] is not None:
+            n_mine = hi - lo
+            pick = numpy.sort(numpy.random.RandomState(0).choice(n_mine, min(n_mine, DUMP_SAMPLE_ROWS), replace=False))
+            outputs["read_mix_rows"] = pick + lo
+            outputs["read_mix"] = res["read_mix"][torch.from_numpy(pick).to(res["read_mix"].device)].cpu().numpy()
+        dump_outputs(opts.dump_outputs, outputs)
     cells = float(n_rows) * n_haps
     return {
         "metric": "EM restart-iterations/sec over %d restarts run to convergence (cells/sec = x R x H), "

@@ -416,3 +416,24 @@ def test_bench_rank_census_rules():
     assert bench.rank_census(torch, dist, dev, 0, 8, True, "gloo", 8)["ok"]       # (test set-ups share the one GPU over gloo)
     one = bench.rank_census(torch, dist, dev, 0, 1, False, "nccl", 1)
     assert one["ok"] and one["ranks_seen"] == 1 and one["backend"] is None
+
+
+def test_bench_dump_outputs_writes_float64_within_its_limit(tmp_path):
+    """bench.py --dump-outputs: one float64 .npy per array (whatever dtype it came in), nothing written when the arrays
+    together exceed DUMP_MAX_BYTES, and --steps below one refused before any work."""
+    import sys
+    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    import bench
+    opts = bench.parse_args(["--steps", "7", "--dump-outputs", str(tmp_path / "out")])
+    assert opts.steps == 7 and opts.dump_outputs == str(tmp_path / "out")
+    props = numpy.random.RandomState(0).dirichlet(numpy.ones(5), size=2)
+    bench.dump_outputs(opts.dump_outputs, {"props": props, "iters": numpy.array([3, 4], dtype=numpy.int64)})
+    assert sorted(os.listdir(opts.dump_outputs)) == ["iters.npy", "props.npy"]
+    got = numpy.load(os.path.join(opts.dump_outputs, "props.npy"))
+    assert got.dtype == numpy.float64 and numpy.array_equal(got, props)
+    assert numpy.load(os.path.join(opts.dump_outputs, "iters.npy")).tolist() == [3.0, 4.0]
+    with pytest.raises(SystemExit):
+        bench.dump_outputs(str(tmp_path / "big"), {"x": numpy.zeros(bench.DUMP_MAX_BYTES // 8 + 1)})
+    assert not os.path.exists(tmp_path / "big")
+    with pytest.raises(SystemExit, match="--steps"):
+        bench.main(["--steps", "0"])
