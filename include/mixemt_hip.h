@@ -54,8 +54,9 @@ extern "C" {
  * 505: mxm_exchange_reduce; 506: mxm_expand_tables;
  * 600 round 6: mxm_restart_tile_coded (three restarts share a pass over records beside a quad dictionary:
  * mxm_em_iter_coded / mxm_em_loop_coded take full tiles of three through em_iter_quad_batched_kernel),
- * mxm_quad_loop_min_rows. */
-#define MXM_VERSION 600
+ * mxm_quad_loop_min_rows;
+ * 601: mxm_observe_bases (the pileup of mixemt's variant check). */
+#define MXM_VERSION 601
 
 /* per-restart loop state, written by mxm_m_finalize (24 bytes); allocate it ZEROED */
 typedef struct mxm_em_state {
@@ -567,6 +568,23 @@ int  mxm_bam_sizes_of(const mxm_bam *bam, mxm_bam_sizes *sizes);
 int  mxm_bam_columns(const mxm_bam *bam, mxm_aln_columns *cols);
 int  mxm_bam_fetch_names(const mxm_bam *bam, char *names, int64_t *name_off, int32_t *ref_id, uint16_t *flag);
 void mxm_bam_free(mxm_bam *bam);
+
+/*
+ * The pileup of the variant check: observe.ObservedBases(alns, mapq=min_mq, baseq=min_bq) (observe.py:56-86), counted
+ * on the device.  `cols` is a HOST struct whose arrays are DEVICE pointers (frag / n_frag are not read); cigar and seq
+ * must be non-NULL (a 1-element array when empty), qual / has_qual as in mxm_aln_encode; is_reverse[n_aln] nullable
+ * (NULL = every alignment forward).  counts[L][16] (uint32, ZEROED by the caller, accumulated into) per reference
+ * position: bins 0-6 forward A C G T N other '-', 7-13 reverse a c g t n other '+', 14-15 pad (left alone).
+ *   alignments with mapq < min_mq or ref_start < 0 are skipped; under M / = / X each base counts once: upper-cased,
+ *   'N' when the alignment has qualities and the base's is < min_bq, a character other than ACGTN in `other`;
+ *   each reference position under D or N counts a gap; I / S advance the query, H / P nothing
+ * The table is the same bits for any alignment order and any split of the alignments over calls.  HOST, blocking
+ * (stream-ordered scratch of its own; returns once the stream has finished the call's work).  Returns 0, -1 (bad
+ * arguments, or an alignment reaching position L or beyond), -2 (HIP error), -4 (a CIGAR that runs past its sequence
+ * or holds an unknown operation, as mxm_aln_encode); after -1 / -4 the table's contents are unspecified.
+ */
+int  mxm_observe_bases(const mxm_aln_columns *cols, const uint8_t *is_reverse, int32_t min_mq, int32_t min_bq, int64_t L,
+                       uint32_t *counts, void *stream);
 
 /*
  * One-shot exchange of the M-step sums between the ranks of a row-sharded loop -- OPTIONAL, instead of the all-reduce

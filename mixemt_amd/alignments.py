@@ -40,9 +40,11 @@ class AlignmentColumns(object):
         ref_start[n] int64, mapq[n] int32, frag[n] int64 (index into `names`), cig_ptr[n+1] / cigar[] uint32
         (BAM encoding: length << 4 | op), seq_ptr[n+1] / seq[] uint8 (ASCII) / qual[] uint8, has_qual[n] uint8
     names: the fragments' query_names (list, or any indexable), mates sharing one.
+    is_reverse[n] uint8 (optional; None = every alignment forward): the strand, read only by the pileup
+        (observe.observe_bases); the encoder does not look at it.
     """
 
-    def __init__(self, ref_start, mapq, frag, cig_ptr, cigar, seq_ptr, seq, qual, has_qual, names):
+    def __init__(self, ref_start, mapq, frag, cig_ptr, cigar, seq_ptr, seq, qual, has_qual, names, is_reverse=None):
         self.ref_start = numpy.ascontiguousarray(ref_start, dtype=numpy.int64)
         self.mapq = numpy.ascontiguousarray(mapq, dtype=numpy.int32)
         self.frag = numpy.ascontiguousarray(frag, dtype=numpy.int64)
@@ -53,8 +55,10 @@ class AlignmentColumns(object):
         self.qual = None if qual is None else numpy.ascontiguousarray(qual, dtype=numpy.uint8)
         self.has_qual = None if has_qual is None else numpy.ascontiguousarray(has_qual, dtype=numpy.uint8)
         self.names = names
+        self.is_reverse = None if is_reverse is None else numpy.ascontiguousarray(is_reverse, dtype=numpy.uint8)
         n = len(self.ref_start)
-        if not (len(self.mapq) == len(self.frag) == n and len(self.cig_ptr) == len(self.seq_ptr) == n + 1):
+        if not (len(self.mapq) == len(self.frag) == n and len(self.cig_ptr) == len(self.seq_ptr) == n + 1
+                and (self.is_reverse is None or len(self.is_reverse) == n)):
             raise ValueError("alignment columns of different lengths")
         if n and (int(self.cig_ptr[-1]) > len(self.cigar) or int(self.seq_ptr[-1]) > len(self.seq)
                   or (self.qual is not None and len(self.qual) < len(self.seq))
@@ -77,14 +81,15 @@ class AlignmentColumns(object):
     def from_alignments(cls, alns):
         """
         pysam.AlignedSegment-like objects -> columns: one pass, a handful of attribute reads per ALIGNMENT (none per
-        base).  Uses `cigartuples` where the object has it (pysam), else parses `cigarstring`.  Raises NeedsSlowPath
+        base).  Uses `cigartuples` where the object has it (pysam), else parses `cigarstring`; `is_reverse` becomes a
+        column when the objects have it (absent on one: forward).  Raises NeedsSlowPath
         for what cannot be held as bytes (non-ASCII sequence text, a quality array of another length).
         """
-        starts, mapqs, frags, cig_len, seq_len, has_q = [], [], [], [], [], []
+        starts, mapqs, frags, cig_len, seq_len, has_q, rev = [], [], [], [], [], [], []
         cig, seqs, quals = [], [], []
         ids = {}
         names = []
-        any_q = False
+        any_q = any_strand = False
         for aln in alns:
             name = aln.query_name
             f = ids.get(name)
@@ -94,6 +99,10 @@ class AlignmentColumns(object):
             frags.append(f)
             starts.append(aln.reference_start if aln.reference_start is not None else -1)
             mapqs.append(aln.mapping_quality)
+            strand = getattr(aln, "is_reverse", None)
+            if strand is not None:
+                any_strand = True
+            rev.append(1 if strand else 0)
             tuples = getattr(aln, "cigartuples", None)
             if tuples is None:
                 text = getattr(aln, "cigarstring", None) or ""
@@ -134,7 +143,8 @@ class AlignmentColumns(object):
                         raise NeedsSlowPath("base quality outside 0..255")
                     qual[seq_ptr[i]:seq_ptr[i + 1]] = arr
         return cls(starts, mapqs, frags, cig_ptr, numpy.asarray(cig, dtype=numpy.uint32), seq_ptr, seq, qual,
-                   numpy.asarray(has_q, dtype=numpy.uint8), names)
+                   numpy.asarray(has_q, dtype=numpy.uint8), names,
+                   numpy.asarray(rev, dtype=numpy.uint8) if any_strand else None)
 
     def struct(self):
         """(mxm_aln_columns, the arrays it points into)."""
@@ -176,7 +186,7 @@ def read_bam(path, n_threads=0):
     A BAM file -> AlignmentColumns through the library's reader (mxm_bam_read, csrc/bam_reader.hpp): what the reference
     gets from `pysam.AlignmentFile(path).fetch()` (bin/mixemt:139-147, preprocess.py:209) -- every record placed on a
     reference, in file order -- without a Python object per alignment.  The columns carry `.ref_id`, `.flag` (per
-    alignment, not used by the encoder) and `.bam_counts` = (records in the file, skipped because unplaced).
+    alignment, not used by the encoder), `.is_reverse` (FLAG 0x10, pysam's is_reverse) and `.bam_counts` = (records in the file, skipped because unplaced).
     Raises OSError when the file cannot be read, ValueError when it is not a BAM file the reader takes.
     """
     import ctypes
@@ -218,7 +228,8 @@ def read_bam(path, n_threads=0):
                             view(st.cig_ptr, n + 1, numpy.int64), view(st.cigar, sz.n_cigar, numpy.uint32),
                             view(st.seq_ptr, n + 1, numpy.int64), view(st.seq, sz.n_bases, numpy.uint8),
                             view(st.qual, sz.n_bases, numpy.uint8) if st.qual else None,
-                            view(st.has_qual, n, numpy.uint8), FragmentNames(names, name_off))
+                            view(st.has_qual, n, numpy.uint8), FragmentNames(names, name_off),
+                            ((flag & 0x10) != 0).astype(numpy.uint8))
     cols.ref_id, cols.flag = ref_id, flag
     cols.bam_counts = (int(sz.n_records_total), int(sz.n_skipped_unplaced))
     return cols

@@ -6,6 +6,9 @@ resident, and they remove the 43 GB device->host copy of `read_mix` the
 reference's NumPy versions would need:
 
     find_contribs_from_reads   <- assemble._find_contribs_from_reads  assemble.py:103-123
+    get_contributors (+ _records) <- assemble.get_contributors        assemble.py:31-100
+    check_contrib_phy_vars     <- assemble._check_contrib_phy_vars    assemble.py:126-208 (host logic over the pileup of
+                                  observe.observe_bases)
     read_votes / report_read_votes <- stats.report_read_votes          stats.py:34-45
     update_contribs            <- assemble.update_contribs             assemble.py:211-230
     assign_read_indexes        <- assemble.assign_read_indexes         assemble.py:284-334
@@ -144,6 +147,91 @@ def find_contribs_from_reads(read_hap_mat, wts, args):
     """
     best, votes = _row_argmax_votes_device(read_hap_mat, wts)
     return _contributors_on_device(best, votes, votes.numel(), args.min_reads)[0]
+
+
+def check_contrib_phy_vars(phylo, obs, contrib_prop, args):
+    """
+    assemble._check_contrib_phy_vars (assemble.py:126-208): from the largest proportion down, a candidate is kept when
+    enough of its variants that no kept candidate has already claimed are seen in the sample -- a (pos, derived base)
+    is seen when obs.obs_at(pos, der) >= max(args.min_var_reads, obs.total_obs(pos) * args.frac_var_reads); kept when
+    it has no such variants, or args.var_count is set and met, or the seen fraction is >= args.var_fraction.  A kept
+    candidate's seen variants and its ancestral bases (phylo.get_ancestral) are claimed.  `obs`: an
+    observe.ObservedBases (or the reference's).  contrib_prop: [[haplogroup, proportion], ...] by descending proportion.
+    Verbose lines go to stderr, as the reference writes them.
+    """
+    from .phylotree import der_allele, pos_from_var
+    used_vars = set()
+    ignore_haps = set()
+    threshold = 0                                  # (the reference's "Keeping" line prints the last site's threshold)
+    if args.verbose:
+        sys.stderr.write("Checking diagnostic variants:\n")
+    for hap, _ in contrib_prop:
+        uniq_vars = set((pos_from_var(var), der_allele(var)) for var in phylo.hap_var[hap])
+        uniq_vars -= used_vars
+        if args.verbose:
+            sys.stderr.write("%s (%d unique variants)\n" % (hap, len(uniq_vars)))
+        found_vars = set()
+        for pos, der in sorted(uniq_vars):
+            seen, total = obs.obs_at(pos, der), obs.total_obs(pos)
+            if args.verbose:
+                var = "%d%s" % (pos + 1, der)
+                sys.stderr.write("  %s: %d/%d\n" % (var.rjust(6), seen, total))
+            threshold = max(args.min_var_reads, total * args.frac_var_reads)
+            if seen >= threshold:
+                found_vars.add((pos, der))
+        if (len(uniq_vars) == 0
+                or (args.var_count is not None and len(found_vars) >= args.var_count)
+                or (float(len(found_vars)) / len(uniq_vars) >= args.var_fraction)):
+            if args.verbose:
+                sys.stderr.write("Keeping '%s': %d/%d unique variant bases observed at least %d times.\n"
+                                 % (hap, len(found_vars), len(uniq_vars), threshold))
+            used_vars.update(found_vars)
+            used_vars.update(phylo.get_ancestral(hap))
+        else:
+            if args.verbose:
+                sys.stderr.write("Ignoring '%s': only %d/%d unique variant bases observed.\n"
+                                 % (hap, len(found_vars), len(uniq_vars)))
+            ignore_haps.add(hap)
+    return [con for con in contrib_prop if con[0] not in ignore_haps]
+
+
+def _contributor_table(phylo, obs, haplogroups, props, find, args):
+    """assemble.get_contributors (assemble.py:31-100) around a candidate finder `find()` -> column indexes."""
+    if not getattr(args, "contributors", None):
+        contributors = find()
+    else:
+        contributors = []
+        for con in args.contributors.split(","):
+            try:
+                contributors.append(haplogroups.index(con))
+            except ValueError:
+                raise ValueError("Unknown haplogroup '%s'" % (con))
+    contrib_prop = [[haplogroups[con], props[con]] for con in contributors]
+    contrib_prop.sort(key=lambda con: con[1], reverse=True)
+    if args.var_check and not getattr(args, "contributors", None):
+        contrib_prop = check_contrib_phy_vars(phylo, obs, contrib_prop, args)
+    name_fmt = "hap%%0%dd" % (len(str(len(contrib_prop) + 1)))
+    for num, con in enumerate(contrib_prop):
+        con.insert(0, name_fmt % (num + 1))
+    return contrib_prop
+
+
+def get_contributors(phylo, obs, haplogroups, wts, em_results, args):
+    """
+    assemble.get_contributors (assemble.py:31-100): [[hapNN, haplogroup, proportion], ...] by descending proportion --
+    the candidates with at least args.min_reads votes (or args.contributors, comma-separated: ValueError for an unknown
+    one), filtered by check_contrib_phy_vars when args.var_check and no args.contributors.  em_results = (props,
+    read_hap_mat) with the posterior matrix dense (numpy or device).
+    """
+    props, read_hap_mat = em_results
+    return _contributor_table(phylo, obs, haplogroups, props,
+                              lambda: find_contribs_from_reads(read_hap_mat, wts, args), args)
+
+
+def get_contributors_records(phylo, obs, haplogroups, wts, props, cm, ln_theta_k, args):
+    """get_contributors for a matrix held as records (no posterior matrix): the candidates of find_contribs_from_records."""
+    return _contributor_table(phylo, obs, haplogroups, props,
+                              lambda: find_contribs_from_records(cm, ln_theta_k, wts, args), args)
 
 
 def read_votes(read_hap_mat):

@@ -28,6 +28,7 @@
 //   fused_coded_kernels.hpp  em_fused_coded_kernel (the whole EM loop over records in one persistent launch)
 //   fused_narrow_kernels.hpp  em_fused_narrow_kernel (the same for the refinement EM's few columns: the matrix in registers)
 //   aln_encode.hpp      HOST code: mxm_aln_encode, the batched alignment front end (process_reads + reduce_reads + row order)
+//   observe_kernels.hpp observe_bucket_kernel, observe_count_kernel (the pileup of the variant check: observe.py:56-86)
 // This file: the host side of the C ABI (shape checks, grid sizing, dispatch, the loop driver).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -63,6 +64,7 @@
 #include "fused_coded_kernels.hpp"
 #include "fused_narrow_kernels.hpp"
 #include "exchange.hpp"
+#include "observe_kernels.hpp"
 
 
 // ------------------------------------------------------------------------------------------
@@ -2203,5 +2205,62 @@ extern "C" int mxm_fold_logaddexp(double *acc, int64_t lda, const double *const 
         hipLaunchKernelGGL(fold_logaddexp_kernel<false>, dim3(grid), dim3(256), 0, (hipStream_t)stream, acc, lda, in,
                            (int)n_in, R, (int)H, delta);
     HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// The pileup (observe_kernels.hpp).  Blocking: the scratch is stream-ordered memory of the call's own, and the error word
+// is read back before returning.
+extern "C" int mxm_observe_bases(const mxm_aln_columns *cols, const uint8_t *is_reverse, int32_t min_mq, int32_t min_bq,
+                                 int64_t L, uint32_t *counts, void *stream) {
+    if (cols == nullptr || cols->n_aln < 0 || L < 0 || (L > 0 && counts == nullptr))
+        return fail(-1, "mxm_observe_bases: bad arguments%s", "");
+    const int64_t n = cols->n_aln;
+    if (n == 0) return 0;
+    if (n > 0x7fffffffLL) return fail(-1, "mxm_observe_bases: more than 2^31 - 1 alignments%s (%lld)", "", n);
+    if (cols->ref_start == nullptr || cols->mapq == nullptr || cols->cig_ptr == nullptr || cols->cigar == nullptr ||
+        cols->seq_ptr == nullptr || cols->seq == nullptr)
+        return fail(-1, "mxm_observe_bases: ref_start, mapq, cig_ptr, cigar, seq_ptr and seq are required%s", "");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nb = (L + OBS_BUCKET - 1) / OBS_BUCKET;
+    // scratch: cnt[nb], cursor[nb], off[nb + 1], chunk_off[nb + 1], err, then perm[n] (int32)
+    const size_t words = (size_t)(4 * nb + 3);
+    void *scratch = nullptr;
+    HIP_TRY(hipMallocAsync(&scratch, words * 8 + (size_t)n * 4, s));
+    unsigned long long *cnt = static_cast<unsigned long long *>(scratch), *cursor = cnt + nb, *off = cursor + nb,
+                       *chunk_off = off + nb + 1, *err = chunk_off + nb + 1;
+    int32_t *perm = reinterpret_cast<int32_t *>(err + 1);
+    unsigned long long err_host = OBS_ERR_NONE;
+    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)nb * 8, s);
+    if (e == hipSuccess) e = hipMemsetAsync(err, 0xff, 8, s);
+    if (e == hipSuccess) {
+        const unsigned grid_b = (unsigned)((n + OBS_BKT_PER_WG - 1) / OBS_BKT_PER_WG);
+        hipLaunchKernelGGL(observe_bucket_kernel<0>, dim3(grid_b), dim3(OBS_BKT_THREADS), 0, s, cols->ref_start, cols->mapq, n,
+                           min_mq, L, nb, cnt, perm, err);
+        hipLaunchKernelGGL(observe_scan_kernel, dim3(1), dim3(1024), 0, s, cnt, nb, off, chunk_off, cursor);
+        hipLaunchKernelGGL(observe_bucket_kernel<1>, dim3(grid_b), dim3(OBS_BKT_THREADS), 0, s, cols->ref_start, cols->mapq, n,
+                           min_mq, L, nb, cursor, perm, err);
+        // at most one partial chunk per bucket beyond the full ones
+        const int64_t grid_c = (n + OBS_CHUNK - 1) / OBS_CHUNK + nb;
+        if (grid_c > 0x7fffffffLL) e = hipErrorInvalidValue;
+        else {
+            hipLaunchKernelGGL(observe_count_kernel, dim3((unsigned)grid_c), dim3(OBS_THREADS), 0, s, cols->ref_start,
+                               cols->cig_ptr, cols->cigar, cols->seq_ptr, cols->seq, cols->qual, cols->has_qual, is_reverse,
+                               min_bq, L, nb, off, chunk_off, perm, counts, err);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(&err_host, err, 8, hipMemcpyDeviceToHost, s);
+    }
+    const hipError_t ef = hipFreeAsync(scratch, s);
+    if (e == hipSuccess) e = ef;
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    HIP_TRY(e);
+    if (err_host != OBS_ERR_NONE) {
+        const long long i = (long long)(err_host >> 2);
+        switch ((int)(err_host & 3)) {
+            case 1: return fail(-4, "mxm_observe_bases: the CIGAR of alignment %s%lld runs past its sequence", "", i);
+            case 2: return fail(-4, "mxm_observe_bases: the CIGAR of alignment %s%lld holds an unknown operation", "", i);
+            default: return fail(-1, "mxm_observe_bases: alignment %s%lld reaches past the table (L = %lld)", "", i, L);
+        }
+    }
     return 0;
 }

@@ -95,3 +95,28 @@ def load_prev(prefix, mmap=False):
         sys.stderr.write("Contribution estimate refinement will be skipped\n")
         init_mat = None
     return haps, reads, wts, init_mat, (props, read_hap_mat)
+
+
+def write_base_obs(out, obs, ref, prefix=""):
+    """
+    stats.write_base_obs (stats.py:72-93), the `-t` PREFIX.obs.tab rows: per reference position the position (0-based),
+    the A / C / G / T counts of both strands and the total of every observation there (N, gaps and other characters
+    included).  `obs` is an observe.ObservedBases (counted from its table) or any object with the reference's obs_at /
+    obs_tab.
+    """
+    if prefix:
+        prefix += "\t"
+    n = len(ref)
+    counts = getattr(obs, "counts", None)
+    if counts is None:
+        for pos in range(n):
+            out.write("%s%d\t%s\t%d\n" % (prefix, pos, "\t".join(str(obs.obs_at(pos, base)) for base in "ACGT"),
+                                          sum(obs.obs_tab[pos].values())))
+        return
+    tab = numpy.zeros((n, 16), dtype=numpy.int64)
+    m = min(n, counts.shape[0])
+    tab[:m] = counts[:m]
+    acgt = tab[:, 0:4] + tab[:, 7:11]
+    total = tab[:, :14].sum(axis=1)
+    out.write("".join("%s%d\t%d\t%d\t%d\t%d\t%d\n" % (prefix, pos, a, c, g, t, tot)
+                      for pos, (a, c, g, t), tot in zip(range(n), acgt.tolist(), total.tolist())))

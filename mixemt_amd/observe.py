@@ -1,0 +1,202 @@
+"""
+The pileup of mixemt's variant check -- observe.ObservedBases (the reference's mixemt/observe.py), counted on the device:
+
+    obs = observe_bases(cols, min_mq=30, min_bq=30, ref_len=len(refseq))     # cols: alignments.AlignmentColumns
+    obs.counts                  uint32 [L][16]: per position the bins of mxm_observe_bases (BINS below)
+    obs.obs_at(pos, base=None, stranded=False), obs.total_obs(pos)            the reference's queries (observe.py:88-145)
+    obs.obs_tab[pos]            a Counter of the position's observations, as the reference's attribute holds them
+
+The reference walks pysam's get_aligned_pairs(matches_only=False) one tuple at a time (observe.py:56-86); here one
+library call (mxm_observe_bases, csrc/observe_kernels.hpp) counts every alignment's bases and gaps into the table.
+A character other than ACGTN is counted in the `other` bin of its strand: the reference keys it by the character itself;
+here it appears as 'X' (forward) / 'x' (reverse) in obs_at(pos) and obs_tab, and in write_base_obs' totals.
+"""
+
+import collections
+import collections.abc
+import ctypes
+import warnings
+
+import numpy
+
+from . import _lib
+from ._dev import current_stream, require_gpu, torch
+
+# bins of a row of the table: forward, then reverse, then two pad bins
+BINS = "ACGTNX-acgtnx+"
+_FWD = {c: i for i, c in enumerate("ACGTNX-")}
+
+
+def pileup_length(cols, min_mq=30, ref_len=None):
+    """L = max(ref_len, the largest reference end of an alignment that is counted), from the CIGARs on the host."""
+    n = len(cols)
+    end = 0
+    if n:
+        ops = cols.cigar & 15
+        lens = (cols.cigar >> 4).astype(numpy.int64)
+        lens[(ops != 0) & (ops != 2) & (ops != 3) & (ops != 7) & (ops != 8)] = 0      # ops that advance the reference
+        cum = numpy.zeros(len(lens) + 1, dtype=numpy.int64)
+        numpy.cumsum(lens, out=cum[1:])
+        span = cum[cols.cig_ptr[1:]] - cum[cols.cig_ptr[:-1]]
+        use = (cols.mapq >= min_mq) & (cols.ref_start >= 0)
+        if use.any():
+            end = int((cols.ref_start[use] + span[use]).max())
+    return max(int(ref_len or 0), end)
+
+
+class DeviceColumns(object):
+    """AlignmentColumns uploaded for mxm_observe_bases (.upload_s: the host -> device copy's time)."""
+
+    def __init__(self, cols, dev=None):
+        import time
+        dev = dev or require_gpu()
+        t0 = time.perf_counter()
+
+        def up(arr, dtype, view=None):
+            if arr is None:
+                return None
+            arr = numpy.ascontiguousarray(arr, dtype=dtype)
+            if view is not None:
+                arr = arr.view(view)
+            if arr.size == 0:
+                arr = numpy.zeros(1, dtype=arr.dtype)               # (the ABI wants a pointer even when empty)
+            with warnings.catch_warnings():                         # read_bam's columns are read-only views
+                warnings.simplefilter("ignore", UserWarning)
+                return torch.from_numpy(arr).to(dev)
+
+        self.n_aln = len(cols)
+        self.ref_start = up(cols.ref_start, numpy.int64)
+        self.mapq = up(cols.mapq, numpy.int32)
+        self.cig_ptr = up(cols.cig_ptr, numpy.int64)
+        self.cigar = up(cols.cigar, numpy.uint32, numpy.int32)
+        self.seq_ptr = up(cols.seq_ptr, numpy.int64)
+        self.seq = up(cols.seq, numpy.uint8)
+        self.qual = up(cols.qual, numpy.uint8)
+        self.has_qual = up(cols.has_qual, numpy.uint8)
+        self.is_reverse = up(getattr(cols, "is_reverse", None), numpy.uint8)
+        torch.cuda.synchronize()
+        self.upload_s = time.perf_counter() - t0
+
+    def struct(self):
+        def p(t):
+            return None if t is None else t.data_ptr()
+
+        return _lib.AlnColumns(self.n_aln, 0, p(self.ref_start), p(self.mapq), None, p(self.cig_ptr), p(self.cigar),
+                               p(self.seq_ptr), p(self.seq), p(self.qual), p(self.has_qual))
+
+
+def count_bases(dcols, counts, min_mq=30, min_bq=30):
+    """
+    mxm_observe_bases: add the pileup of the uploaded columns `dcols` to `counts` (a zeroed or earlier-filled int32
+    device tensor [L][16]).  Raises ValueError with the library's message (a CIGAR that runs past its sequence or holds
+    an unknown operation; an alignment past the table).
+    """
+    if counts.dim() != 2 or counts.shape[1] != 16 or counts.dtype != torch.int32 or not counts.is_contiguous():
+        raise ValueError("counts must be a contiguous int32 [L][16] device tensor")
+    lib = _lib.load()
+    st = dcols.struct()
+    rev = 0 if dcols.is_reverse is None else dcols.is_reverse.data_ptr()
+    _lib.check(lib.mxm_observe_bases(ctypes.byref(st), rev, int(min_mq), int(min_bq), int(counts.shape[0]),
+                                     counts.data_ptr(), current_stream()), "mxm_observe_bases")
+    return counts
+
+
+def observe_bases(cols, min_mq=30, min_bq=30, ref_len=None):
+    """ObservedBases(alns, mapq=min_mq, baseq=min_bq) of the reference for alignments held as columns."""
+    dev = require_gpu()
+    L = pileup_length(cols, min_mq, ref_len)
+    dcols = DeviceColumns(cols, dev)
+    counts = torch.zeros((L, 16), dtype=torch.int32, device=dev)
+    count_bases(dcols, counts, min_mq, min_bq)
+    obs = ObservedBases(counts.cpu().numpy().view(numpy.uint32), min_mq, min_bq)
+    obs.upload_s = dcols.upload_s
+    return obs
+
+
+class ObservedBases(object):
+    """
+    The reference's ObservedBases over a counted table (observe.py:16-145): counts[L][16] uint32 in the bins of BINS.
+    Positions past the table have no observations.
+    """
+
+    def __init__(self, counts, mapq=30, baseq=30):
+        self.counts = numpy.asarray(counts)
+        if self.counts.ndim != 2 or self.counts.shape[1] != 16:
+            raise ValueError("counts must be [L][16]")
+        self.min_map_qual = mapq
+        self.min_base_qual = baseq
+        self.obs_tab = _ObsTabView(self.counts)
+
+    def _row(self, pos):
+        pos = int(pos)
+        if 0 <= pos < self.counts.shape[0]:
+            return self.counts[pos]
+        return None
+
+    def obs_at(self, pos, base=None, stranded=False):
+        """observe.py:88-132: a Counter (base None), an int, or a (forward, reverse) tuple; ValueError for a bad base."""
+        row = self._row(pos)
+        if base is None:
+            out = collections.Counter()
+            if row is None:
+                return out
+            if stranded:
+                for i, key in enumerate(BINS):
+                    if row[i]:
+                        out[key] = int(row[i])
+                return out
+            for i, key in enumerate(BINS):
+                if row[i]:
+                    out["-" if key == "+" else key.upper()] += int(row[i])
+            return out
+        # (substring tests, as the reference's: '' or 'AC' pass the first and count nothing, '-+' the second)
+        if base.upper() in "ACGTN":
+            i = _FWD.get(base.upper())
+        elif base in "-+":
+            i = _FWD["-"]
+        else:
+            raise ValueError("Bad base: %s" % (base))
+        fwd, rev = (0, 0) if row is None or i is None else (int(row[i]), int(row[i + 7]))
+        if stranded:
+            return (fwd, rev)
+        return fwd + rev
+
+    def total_obs(self, pos):
+        """observe.py:134-145: A + C + G + T of both strands (not N, not gaps)."""
+        row = self._row(pos)
+        if row is None:
+            return 0
+        return int(row[0:4].sum(dtype=numpy.int64) + row[7:11].sum(dtype=numpy.int64))
+
+
+class _ObsTabView(collections.abc.Mapping):
+    """Read-only pos -> Counter view of the table (the reference's obs_tab); any position gives a Counter."""
+
+    def __init__(self, counts):
+        self._counts = counts
+
+    def __getitem__(self, pos):
+        out = collections.Counter()
+        pos = int(pos)
+        if 0 <= pos < self._counts.shape[0]:
+            row = self._counts[pos]
+            for i, key in enumerate(BINS):
+                if row[i]:
+                    out[key] = int(row[i])
+        return out
+
+    def _observed(self):
+        return numpy.flatnonzero(self._counts[:, :14].any(axis=1))
+
+    def __iter__(self):
+        return (int(p) for p in self._observed())
+
+    def __len__(self):
+        return len(self._observed())
+
+    def __contains__(self, pos):
+        try:
+            pos = int(pos)
+        except (TypeError, ValueError):
+            return False
+        return 0 <= pos < self._counts.shape[0] and bool(self._counts[pos, :14].any())

@@ -193,6 +193,16 @@ class Phylotree(object):
         """Sorted 0-based variant sites (reference: phylotree.py:221)."""
         return sorted(self.variants.keys())
 
+    def get_ancestral(self, hap_id):
+        """
+        (0-based position, reference base) of every variant site that no variant of `hap_id` touches, in the
+        reference's order (phylotree.py:317-336: variant sites ascending).
+        """
+        ancestral = {pos: self.refseq[pos] for pos in self.get_variant_pos()}
+        for var in self.hap_var[hap_id]:
+            ancestral.pop(pos_from_var(var), None)
+        return list(ancestral.items())
+
     def add_custom_hap(self, hap_id, variants):
         """Reference: phylotree.py:231-251 (ValueError on a name clash)."""
         if hap_id in self.hap_var:

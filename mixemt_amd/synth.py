@@ -195,6 +195,8 @@ def synth_alignments(tables, refseq, n_frag, seed=1, contrib=DEFAULT_CONTRIB, pr
     five fixed starts with length 120 (equal signatures: weights > 1); mates overlap their fragment's first read by
     20-60 bases, and half of them get one substituted base inside the overlap (half of those at low quality) -- where
     that base sits on a variant site the fragment sees two different bases there.  Alignment order is shuffled.
+    Strands (is_reverse): every mate reverse, half of the other alignments reverse -- drawn from a stream of their own,
+    so that every other column is what it was before strands existed.
     """
     from .alignments import AlignmentColumns
     rng = numpy.random.default_rng([int(seed), 0xA11])
@@ -222,6 +224,7 @@ def synth_alignments(tables, refseq, n_frag, seed=1, contrib=DEFAULT_CONTRIB, pr
     a_start = numpy.concatenate([start, start[m_idx] + length[m_idx] - overlap])
     n_aln = len(a_frag)
     is_mate = numpy.arange(n_aln) >= n_frag
+    is_reverse = (is_mate | (numpy.random.default_rng([int(seed), 0x5752]).random(n_aln) < 0.5)).astype(numpy.uint8)
     kind = rng.choice(6, size=n_aln)                                     # 0-2 plain, 3 ins, 4 del, 5 clip
     kind[is_mate] = 0
     at = rng.integers(10, 70, size=n_aln)                                # where the indel sits (all lengths are >= 80)
@@ -292,7 +295,7 @@ def synth_alignments(tables, refseq, n_frag, seed=1, contrib=DEFAULT_CONTRIB, pr
         new_cptr, cc_own, cc_off = _ragged(n_ops[perm])
         cigar = cigar[cig_ptr[perm][cc_own] + cc_off]
         seq_ptr, cig_ptr = new_sptr, new_cptr
-        a_start, mapq, a_frag, has_qual = a_start[perm], mapq[perm], a_frag[perm], has_qual[perm]
+        a_start, mapq, a_frag, has_qual, is_reverse = a_start[perm], mapq[perm], a_frag[perm], has_qual[perm], is_reverse[perm]
         # fragment ids in order of first appearance in the file, as a reader's name table would number them
         first = numpy.full(n_frag, n_aln, dtype=numpy.int64)
         numpy.minimum.at(first, a_frag, numpy.arange(n_aln, dtype=numpy.int64))
@@ -301,4 +304,4 @@ def synth_alignments(tables, refseq, n_frag, seed=1, contrib=DEFAULT_CONTRIB, pr
         a_frag = rank[a_frag]
         inv = numpy.argsort(rank)
         names = [names[i] for i in inv]
-    return AlignmentColumns(a_start, mapq, a_frag, cig_ptr, cigar, seq_ptr, seq, qual, has_qual, names)
+    return AlignmentColumns(a_start, mapq, a_frag, cig_ptr, cigar, seq_ptr, seq, qual, has_qual, names, is_reverse)

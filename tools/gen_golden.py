@@ -35,6 +35,10 @@ Fixtures (SURVEY.md section 8 c):
         update_contribs -> assign_read_indexes with a single contributor (bin/mixemt:311-320)
     g12 on-disk formats: the bytes the reference's own dump_all writes (bin/mixemt:214-245) for a small run and what its
         load_prev (bin/mixemt:168-211) reads back from them
+    g16 the variant check: the reference's ObservedBases (observe.py) over ~4 000 synthetic fragments with strands plus
+        hand-made alignments (D, N, an H clip, non-ACGTN bases, an unplaced one, mapq / bq at the 29 / 30 edges) --
+        tests/_pileup_aln.py objects --, its process_reads -> build_em_matrix -> run_em, get_contributors with the
+        check on under four argument sets, write_base_obs bytes and get_ancestral of the candidates
 """
 
 import argparse
@@ -198,6 +202,59 @@ def make_g11_alignments(refseq, tables, n_frag=320, seed=1111):
     alns.append(second)
     order = rng.permutation(len(alns))                            # file order is not fragment order
     return [alns[i] for i in order], "lonely"
+
+
+G16_SEED = 16          # synth_alignments seed of g16 (chosen so that the default check drops >= 1 candidate, keeps >= 2)
+G16_EM_SEED = 7
+G16_MIN_READS = 10
+
+
+def make_g16_alignments(refseq, tables, n_frag=4000):
+    """synth_alignments (with strands) + hand-made alignments for the pileup's edges -> (AlignmentColumns, objects)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from _pileup_aln import PileupAln, from_columns
+    from mixemt_amd import synth
+    from mixemt_amd.alignments import AlignmentColumns
+    cols = synth.synth_alignments(tables, refseq, n_frag, seed=G16_SEED)
+    alns = from_columns(cols)
+    rng = numpy.random.default_rng(1616)
+
+    def seq_at(start, n):
+        return refseq[start:start + n]
+
+    def q(n, v=38):
+        return [v] * n
+
+    M, I, D, N, S, H, P = 0, 1, 2, 3, 4, 5, 6
+    extra = [
+        # deletions and a reference skip, both strands
+        PileupAln("h_del", 700, 60, seq_at(700, 40) + seq_at(745, 40), q(80), [(M, 40), (D, 5), (M, 40)], False),
+        PileupAln("h_del_rev", 702, 60, seq_at(702, 30) + seq_at(735, 30), q(60), [(M, 30), (D, 3), (M, 30)], True),
+        PileupAln("h_skip", 3000, 60, seq_at(3000, 30) + seq_at(3330, 30), q(60), [(M, 30), (N, 300), (M, 30)], False),
+        PileupAln("h_skip_rev", 3010, 60, seq_at(3010, 20) + seq_at(3130, 20), q(40), [(M, 20), (N, 100), (M, 20)], True),
+        # hard clip, soft clip, insertion, padding, '=' and 'X'
+        PileupAln("h_clip", 5000, 60, "GGGG" + seq_at(5000, 50), q(54), [(H, 10), (S, 4), (M, 50), (H, 7)], False),
+        PileupAln("h_ins", 5100, 60, seq_at(5100, 20) + "TT" + seq_at(5120, 20), q(42), [(M, 20), (I, 2), (P, 1), (M, 20)],
+                  True),
+        PileupAln("h_eqx", 5200, 60, seq_at(5200, 30), q(30), [(7, 20), (8, 10)], False),
+        # characters other than ACGTN (and lower case) on both strands
+        PileupAln("h_iupac", 9000, 60, "ACRYacgtnN*" + seq_at(9011, 29), q(40), [(M, 40)], False),
+        PileupAln("h_iupac_rev", 9005, 60, "ryKM" + seq_at(9009, 26), q(30), [(M, 30)], True),
+        # an unplaced alignment, and no quality array
+        PileupAln("h_unplaced", -1, 60, seq_at(0, 30), q(30), [(M, 30)], False),
+        PileupAln("h_noqual", 9100, 60, seq_at(9100, 30), None, [(M, 30)], True),
+        # mapq and base quality at the 29 / 30 edges
+        PileupAln("h_mq29", 9200, 29, seq_at(9200, 30), q(30), [(M, 30)], False),
+        PileupAln("h_mq30", 9200, 30, seq_at(9200, 30), q(30), [(M, 30)], False),
+        PileupAln("h_bq", 9300, 60, seq_at(9300, 40), [29, 30] * 20, [(M, 40)], False),
+        PileupAln("h_bq_rev", 9300, 60, seq_at(9300, 40), [30, 29] * 20, [(M, 40)], True),
+        # a read running off the end of the reference (the table grows past ref_len)
+        PileupAln("h_end", len(refseq) - 20, 60, "ACGT" * 10, q(40), [(M, 40)], False),
+    ]
+    order = rng.permutation(len(alns) + len(extra))
+    every = [(alns + extra)[k] for k in order]
+    cols = AlignmentColumns.from_alignments(every)
+    return cols, from_columns(cols)
 
 
 def main():
@@ -627,6 +684,63 @@ def main():
              contrib_names=numpy.array("\n".join(names)), contrib_haps=numpy.array("\n".join(c[1] for c in contribs)),
              contrib_props=numpy.array([c[2] for c in contribs]), assigned=assigned, vote_text=numpy.array(vote_text),
              props=props, iters=iters, inits=inits, mat_sha256=numpy.array(sha(mat)))
+
+    if want("g16"):
+        for name in ("pysam", "Bio", "Bio.Seq", "Bio.SeqRecord", "Bio.SeqIO"):
+            sys.modules.setdefault(name, types.ModuleType(name))
+        sys.modules["Bio"].SeqIO = sys.modules["Bio.SeqIO"]
+        sys.modules["Bio.Seq"].Seq = object
+        sys.modules["Bio.SeqRecord"].SeqRecord = object
+        import mixemt.assemble
+        import mixemt.observe
+        import mixemt.stats
+        cols, alns = make_g16_alignments(refseq, tables)
+        t0 = time.time()
+        obs = ref.observe.ObservedBases(alns, mapq=30, baseq=30)
+        trip = [(pos, key, cnt) for pos in sorted(obs.obs_tab) for key, cnt in sorted(obs.obs_tab[pos].items())]
+        read_obs = ref.preprocess.process_reads(alns, phy.get_variant_pos(), 30, 30)
+        read_sigs = ref.preprocess.reduce_reads(read_obs)
+        read_sigs.pop("", None)                      # (a fragment conflicted away: the reference dies on it, see g11)
+        rows = sorted(read_sigs)
+        wts = numpy.array([len(read_sigs[r]) for r in rows])
+        mat = ref.preprocess.build_em_matrix(refseq, phy, rows, haps, quiet)
+        props, mix, iters, inits = ref_run_em(ref, mat, wts, G16_EM_SEED)
+        print("g16: pileup + matrix %d x %d + run_em in %.0f s" % (mat.shape[0], mat.shape[1], time.time() - t0), flush=True)
+        base = dict(min_reads=G16_MIN_READS, contributors=None, var_check=True, min_fold=2.0, min_var_reads=3,
+                    frac_var_reads=0.02, var_fraction=0.5, var_count=None)
+        variants = [("default", {}), ("var_count_1", {"var_count": 1}), ("var_fraction_0.9", {"var_fraction": 0.9}),
+                    ("min_var_reads_10", {"min_var_reads": 10})]
+        cand = ref.assemble._find_contribs_from_reads(mix, wts, ns(**base))
+        out = {}
+        for label, kw in variants:
+            a = ns(**dict(base, **kw))
+            got = ref.assemble.get_contributors(phy, obs, haps, wts, (props, mix), a)
+            out["contribs_" + label] = numpy.array("\n".join("%s\t%s\t%r" % (c[0], c[1], float(c[2])) for c in got))
+        a = ns(**dict(base, verbose=True))
+        err, sys.stderr = sys.stderr, io.StringIO()
+        try:
+            ref.assemble.get_contributors(phy, obs, haps, wts, (props, mix), a)
+            verbose_text = sys.stderr.getvalue()
+        finally:
+            sys.stderr = err
+        n_cand, n_kept = len(cand), len(str(out["contribs_default"]).split("\n"))
+        print("g16: %d candidates, %d kept by the default check" % (n_cand, n_kept), flush=True)
+        assert n_kept >= 2 and n_cand - n_kept >= 1, (n_cand, n_kept)
+        buf = io.StringIO()
+        ref.stats.write_base_obs(buf, obs, refseq, prefix="s1")
+        ancestral = {haps[c]: sorted(phy.get_ancestral(haps[c])) for c in cand}
+        import json
+        save("g16_observe", ref_start=cols.ref_start, mapq=cols.mapq, frag=cols.frag, cig_ptr=cols.cig_ptr,
+             cigar=cols.cigar, seq_ptr=cols.seq_ptr, seq=cols.seq, qual=cols.qual, has_qual=cols.has_qual,
+             is_reverse=cols.is_reverse, names=numpy.array("\n".join(cols.names)),
+             seeds=numpy.array([G16_SEED, G16_EM_SEED]), min_reads=numpy.array(G16_MIN_READS),
+             trip_pos=numpy.array([t[0] for t in trip], dtype=numpy.int64),
+             trip_key=numpy.array("".join(t[1] for t in trip)),
+             trip_count=numpy.array([t[2] for t in trip], dtype=numpy.int64),
+             candidates=numpy.array(cand, dtype=numpy.int32), props=props, iters=iters,
+             signatures=numpy.array("\n".join(rows)), weights=wts.astype(numpy.int64),
+             base_obs=numpy.array(buf.getvalue()), verbose_text=numpy.array(verbose_text),
+             ancestral=numpy.array(json.dumps(ancestral)), **out)
 
     if want("g7"):
         cols = list(range(0, 5400, 54))

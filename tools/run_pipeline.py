@@ -7,12 +7,16 @@ synthetic reads, device-resident end to end:
     -> refinement EM on the contributor columns -> read assignment -> contributor table
 
     python tools/run_pipeline.py [--reads N] [--seed S] [--multi M] [--dense [--storage f64|f32|coded|auto]] [--alignments]
-                                 [--pairs | --read-len L]
+                                 [--pairs | --read-len L] [--var-check [-R N] [-F F] [-f F] [-n N]]
 
 --alignments (round 5): start one step earlier, from ALIGNMENTS -- N synthetic fragments (synth-aln-v1: mates, indels,
 clips, low qualities, duplicates) as columns -> the library's batched front end (alignments.encode_alignments =
 process_reads + reduce_reads + the row order of build_em_input, preprocess.py:99-174, :218-225) -> CSR + weights + id
 groups, and the stage is timed beside the others.
+
+--var-check (with --alignments, opt-in): the candidates pass the reference's variant check (assemble.py:126-208; on by
+default in bin/mixemt) over a pileup of the same columns (observe.observe_bases) before the refinement EM; -R / -F / -f /
+-n are bin/mixemt's knobs at its defaults.  Without it the output is what it was.
 
 Default (round 3): the build leaves the matrix as row-dictionary records -- no dense matrix, no posterior matrix; the
 contributors, the vote table and the reduced matrix for the refinement come from the records.  --dense takes the
@@ -48,12 +52,21 @@ def main():
                     help="rows = paired-end fragments (synth-pe-v1: 2 x 150 bp, insert 350-500, mates merged as preprocess.py:118-138 "
                          "merges them): two thirds of them observe more than 64 sites")
     ap.add_argument("--read-len", type=int, default=150, help="length of the single-end reads (synth-v1; 250: 38 %% of the rows above 64 sites)")
+    ap.add_argument("--var-check", action="store_true",
+                    help="with --alignments: the reference's variant check of the candidates (assemble.py:126-208) over "
+                         "a pileup of the same alignments (observe.observe_bases), before the refinement EM")
+    ap.add_argument("-R", "--var-min-reads", dest="min_var_reads", type=int, default=3)
+    ap.add_argument("-F", "--var-fraction-min-reads", dest="frac_var_reads", type=float, default=0.02)
+    ap.add_argument("-f", "--var-fraction", dest="var_fraction", type=float, default=0.5)
+    ap.add_argument("-n", "--var-count", dest="var_count", type=int, default=None)
     ap.add_argument("--threads", type=int, default=0, help="with --alignments: host threads of the encoder (0 = its default)")
     ap.add_argument("--storage", default="auto", choices=["f64", "f32", "coded", "auto"],
                     help="with --dense: form of the matrix the EM loop streams (EmPlan): coded = lossless row dictionaries, "
                          "auto = coded from 1.5e7 cells on")
     opts = ap.parse_args()
     opts.records = not opts.dense
+    if opts.var_check and not opts.alignments:
+        ap.error("--var-check needs --alignments (the pileup is made from the alignments)")
     args = argparse.Namespace(init_alpha=1.0, tolerance=1e-4, max_iter=10000, n_multi=opts.multi,
                               verbose=True, min_reads=10, min_fold=2.0, storage=opts.storage)
     numpy.random.seed(opts.seed)                       # bin/mixemt:507-508
@@ -76,7 +89,7 @@ def main():
             t0 = time.perf_counter()
             tmp = tempfile.TemporaryDirectory()
             bam_path = os.path.join(tmp.name, "synth.bam")
-            _bam_writer.write_bam(bam_path, cols)
+            _bam_writer.write_bam(bam_path, cols, flag=cols.is_reverse.astype(numpy.int64) * 0x10)
             n_written = len(cols)
             sys.stderr.write("written as %s (%.1f MB) in %.1f s (not part of the pipeline)\n"
                              % (bam_path, os.path.getsize(bam_path) / 1e6, time.perf_counter() - t0))
@@ -184,6 +197,25 @@ def main():
     torch.cuda.synchronize()
     sys.stderr.write("contributors from read votes: %.1f ms\n" % ((time.perf_counter() - t0) * 1e3))
     contribs = sorted(([haps[c], props[c]] for c in cons), key=lambda c: c[1], reverse=True)
+    if opts.var_check:
+        from mixemt_amd import observe
+        t0 = time.perf_counter()
+        L = observe.pileup_length(cols, 30, len(refseq))
+        dcols = observe.DeviceColumns(cols)
+        t1 = time.perf_counter()
+        counts = torch.zeros((L, 16), dtype=torch.int32, device="cuda")
+        observe.count_bases(dcols, counts, 30, 30)
+        base_obs = observe.ObservedBases(counts.cpu().numpy().view(numpy.uint32), 30, 30)
+        t2 = time.perf_counter()
+        sys.stderr.write("pileup of %d alignments (observe_bases): %.1f ms on the device + table back, upload of the "
+                         "columns %.1f ms apart\n" % (len(cols), (t2 - t1) * 1e3, dcols.upload_s * 1e3))
+        del dcols
+        chk = argparse.Namespace(min_var_reads=opts.min_var_reads, frac_var_reads=opts.frac_var_reads,
+                                 var_fraction=opts.var_fraction, var_count=opts.var_count, verbose=True)
+        n_cand = len(contribs)
+        contribs = assign.check_contrib_phy_vars(phy, base_obs, contribs, chk)
+        sys.stderr.write("variant check: %d of %d candidates kept in %.1f ms (pileup included)\n"
+                         % (len(contribs), n_cand, (time.perf_counter() - t0) * 1e3))
     fmt = "hap%%0%dd" % len(str(len(contribs) + 1))
     contribs = [[fmt % (i + 1)] + c for i, c in enumerate(contribs)]
     if not contribs:
