@@ -55,8 +55,9 @@ extern "C" {
  * 600 round 6: mxm_restart_tile_coded (three restarts share a pass over records beside a quad dictionary:
  * mxm_em_iter_coded / mxm_em_loop_coded take full tiles of three through em_iter_quad_batched_kernel),
  * mxm_quad_loop_min_rows;
- * 601: mxm_observe_bases (the pileup of mixemt's variant check). */
-#define MXM_VERSION 601
+ * 601: mxm_observe_bases (the pileup of mixemt's variant check);
+ * 602: mxm_observe_bases_labelled (one pileup per label: the per-contributor tables of mixemt's `-t` output). */
+#define MXM_VERSION 602
 
 /* per-restart loop state, written by mxm_m_finalize (24 bytes); allocate it ZEROED */
 typedef struct mxm_em_state {
@@ -585,6 +586,18 @@ void mxm_bam_free(mxm_bam *bam);
  */
 int  mxm_observe_bases(const mxm_aln_columns *cols, const uint8_t *is_reverse, int32_t min_mq, int32_t min_bq, int64_t L,
                        uint32_t *counts, void *stream);
+
+/*
+ * mxm_observe_bases split by label, in ONE call: alignment i with label[i] (DEVICE int32[n_aln]) in [0, n_labels) is
+ * counted, as mxm_observe_bases counts it, into table counts[label[i]][L][16] (uint32, n_labels tables back to back,
+ * ZEROED by the caller, accumulated into); label[i] < 0: not counted.  Each table is the same bits as
+ * mxm_observe_bases over that label's alignments alone, for any alignment order.  (stats.write_statistics, stats.py:138-171:
+ * ObservedBases of each contributor's reads.)  Returns as mxm_observe_bases, and -1 for a label >= n_labels, naming the
+ * first such alignment in index order.
+ */
+int  mxm_observe_bases_labelled(const mxm_aln_columns *cols, const uint8_t *is_reverse, const int32_t *label,
+                                int32_t n_labels, int32_t min_mq, int32_t min_bq, int64_t L, uint32_t *counts,
+                                void *stream);
 
 /*
  * One-shot exchange of the M-step sums between the ranks of a row-sharded loop -- OPTIONAL, instead of the all-reduce

@@ -148,6 +148,8 @@ SIGNATURES = {
     "mxm_bam_fetch_names": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr]),
     "mxm_bam_free": (None, [c_ptr]),
     "mxm_observe_bases": (ctypes.c_int, [ctypes.POINTER(AlnColumns), c_ptr, c_i32, c_i32, c_i64, c_ptr, c_ptr]),
+    "mxm_observe_bases_labelled": (ctypes.c_int, [ctypes.POINTER(AlnColumns), c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i64,
+                                                  c_ptr, c_ptr]),
     "mxm_set_compact_restarts": (ctypes.c_int, [c_i32]),
     "mxm_set_loop_graph": (ctypes.c_int, [c_i32]),
     "mxm_set_loop_fused": (ctypes.c_int, [c_i32, c_i32]),
@@ -165,7 +167,7 @@ SIGNATURES = {
 }
 
 # the MXM_VERSION of include/mixemt_hip.h these signatures were written for; load() refuses any other
-ABI_VERSION = 601
+ABI_VERSION = 602
 
 PROGRESS_FN = ctypes.CFUNCTYPE(None, ctypes.POINTER(EmState), c_i32, c_ptr)
 

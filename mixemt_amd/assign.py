@@ -13,6 +13,7 @@ reference's NumPy versions would need:
     update_contribs            <- assemble.update_contribs             assemble.py:211-230
     assign_read_indexes        <- assemble.assign_read_indexes         assemble.py:284-334
                                   (with _find_best_n_for_read :267-281)
+    assign_reads (ContribReads) <- assemble.assign_reads               assemble.py:233-264 (one label per alignment)
 
 Matrices may be numpy arrays (uploaded) or ROCm tensors.
 """
@@ -331,11 +332,16 @@ def assign_read_indexes(contribs, em_results, haps, reads, min_fold):
     min_fold.  One gather kernel (mxm_assign_reads) instead of an argsort of
     all H columns per row; the result is an AssignedReads (one integer per row, sets formed on demand).
     """
+    return _assign_rows(contribs, em_results, haps, len(reads), min_fold)[0]
+
+
+def _assign_rows(contribs, em_results, haps, n_rows, min_fold):
+    """assign_read_indexes' AssignedReads and the per-row ordinals it was made from, still on the device (None with one
+    contributor or fewer: every row is the first's)."""
     props, read_hap_mat = em_results
-    n_rows = len(reads)
     names = [hap_n for hap_n, _, _ in contribs]
     if len(contribs) <= 1:
-        return AssignedReads(numpy.zeros(n_rows, dtype=numpy.int32), names[:1])
+        return AssignedReads(numpy.zeros(n_rows, dtype=numpy.int32), names[:1]), None
     lib = _lib.load()
     dev = require_gpu()
     mat = as_device(read_hap_mat, torch.float64, dev)
@@ -349,4 +355,130 @@ def assign_read_indexes(contribs, em_results, haps, reads, min_fold):
         _lib.check(lib.mxm_assign_reads(mat.data_ptr(), mat.stride(0), lp_d.data_ptr(), cols_d.data_ptr(),
                                         len(cols), n_rows, mat.shape[1], float(numpy.log(min_fold)),
                                         assigned.data_ptr(), current_stream()), "mxm_assign_reads")
-    return AssignedReads(assigned.cpu().numpy(), names)
+    return AssignedReads(assigned.cpu().numpy(), names), assigned
+
+
+class ContribReads(collections.abc.Mapping):
+    """
+    assemble.assign_reads' result -- contributor name -> that contributor's alignments (assemble.py:233-264) -- held as
+    ONE int32 label per alignment on the device: label k < n_contribs is contribs[k], label n_contribs 'unassigned'
+    (two contributors or more), -1 an alignment whose fragment is in no row (it is in no table, as in the reference,
+    where its read id is in no row's list).
+        labels        int32 device tensor [n_aln]; names: the label -> name list
+        len(cr[name]) that contributor's alignment count (the "Reads" column of report_contributors)
+        rows(name)    its alignment indexes (ascending: the file order the reference's lists keep), numpy int64
+        as_dict(alns) the reference's dict: name -> [alns[i] for i in rows(name)] (indexes when alns is None)
+    Behaves like the reference's defaultdict(list): the keys are the names that got alignments (in the order the
+    AssignedReads lists them), and looking up another name adds it as a key with no alignments -- bin/mixemt's
+    report_contributors does that for every contributor before write_statistics iterates the keys.
+    """
+
+    def __init__(self, cols, labels, names, keys, dcols=None):
+        self.cols = cols                                     # alignments.AlignmentColumns the labels index
+        self.labels = labels
+        self.names = list(names)
+        self._keys = list(keys)
+        self._dcols = dcols
+        n_labels = len(self.names)
+        lab = labels[labels >= 0]
+        self._counts = torch.bincount(lab.to(torch.int64), minlength=n_labels).cpu().numpy() if lab.numel() \
+            else numpy.zeros(n_labels, dtype=numpy.int64)
+        self._host = None
+
+    def device_columns(self):
+        """The alignments uploaded for the labelled pileup (observe.DeviceColumns), made once."""
+        if self._dcols is None:
+            from .observe import DeviceColumns
+            self._dcols = DeviceColumns(self.cols, self.labels.device)
+        return self._dcols
+
+    def label_of(self, name):
+        """The label of `name`, or None for a name without one (a key looked up that is no contributor)."""
+        try:
+            return self.names.index(name)
+        except ValueError:
+            return None
+
+    def count(self, name):
+        k = self.label_of(name)
+        return 0 if k is None else int(self._counts[k])
+
+    def rows(self, name):
+        k = self.label_of(name)
+        if k is None or not self._counts[k]:
+            return numpy.zeros(0, dtype=numpy.int64)
+        if self._host is None:
+            self._host = self.labels.cpu().numpy()
+        return numpy.flatnonzero(self._host == k)
+
+    def as_dict(self, alns=None):
+        if alns is None:
+            return {name: self.rows(name).tolist() for name in self._keys}
+        return {name: [alns[i] for i in self.rows(name)] for name in self._keys}
+
+    def __getitem__(self, name):
+        if name not in self._keys:
+            self._keys.append(name)                          # (defaultdict(list): the lookup makes the key)
+        return self.rows(name)
+
+    def __iter__(self):
+        return iter(list(self._keys))
+
+    def __len__(self):
+        return len(self._keys)
+
+    def __contains__(self, name):
+        return name in self._keys
+
+    def __repr__(self):
+        return "ContribReads(%s)" % ", ".join("%s: %d" % (k, self.count(k)) for k in self._keys)
+
+
+def _row_groups(cols, reads):
+    """(ptr, frag) of the rows' fragments: a ReadIdGroups' own arrays, or the reference's list of read-id lists mapped
+    to fragment indexes of cols.names."""
+    if hasattr(reads, "ptr") and hasattr(reads, "frag"):
+        return numpy.asarray(reads.ptr, dtype=numpy.int64), numpy.asarray(reads.frag, dtype=numpy.int64)
+    index = {name: f for f, name in enumerate(cols.names)}
+    lens = [len(ids) for ids in reads]
+    ptr = numpy.zeros(len(lens) + 1, dtype=numpy.int64)
+    numpy.cumsum(lens, out=ptr[1:])
+    frag = numpy.array([index[name] for ids in reads for name in ids], dtype=numpy.int64)
+    return ptr, frag
+
+
+def alignment_labels(frag, ptr, group_frag, row_label, n_frag, no_row=-1):
+    """
+    One int32 label per alignment (device): row_label[row of the alignment's fragment], or `no_row` when its fragment is
+    in no row.  frag: the alignments' fragment indexes; ptr / group_frag: the rows' fragments (ReadIdGroups); row_label:
+    int32 per row.  All device tensors (frag / group_frag int64, ptr int64).
+    """
+    dev = row_label.device
+    frag_label = torch.full((max(int(n_frag), 1),), int(no_row), dtype=torch.int32, device=dev)
+    if group_frag.numel():
+        frag_label[group_frag] = torch.repeat_interleave(row_label, ptr[1:] - ptr[:-1],
+                                                         output_size=int(group_frag.numel()))
+    return frag_label[frag].contiguous() if frag.numel() else torch.zeros(0, dtype=torch.int32, device=dev)
+
+
+def assign_reads(cols, contribs, em_results, haps, reads, args, dcols=None):
+    """
+    assemble.assign_reads (assemble.py:233-264) over alignments held as columns (alignments.AlignmentColumns; the
+    reference re-reads the BAM file and matches query names): assign_read_indexes' rows, then every alignment of a
+    row's fragments goes to that row's contributor (or 'unassigned').  reads: the rows' fragments (the encoder's
+    ReadIdGroups, or the reference's list of read-id lists).  Returns a ContribReads, one label per alignment, made on
+    the device.  dcols: the columns already uploaded (observe.DeviceColumns), reused by write_statistics.
+    """
+    dev = require_gpu()
+    table, assigned = _assign_rows(contribs, em_results, haps, len(reads), args.min_fold)
+    names = [hap_n for hap_n, _, _ in contribs]
+    if len(contribs) > 1:
+        names.append("unassigned")
+        row_label = torch.where(assigned >= 0, assigned, torch.full_like(assigned, len(contribs)))
+    else:
+        row_label = torch.zeros(len(reads), dtype=torch.int32, device=dev)
+    ptr, group_frag = _row_groups(cols, reads)
+    n_frag = max(len(cols.names), int(cols.frag.max()) + 1 if len(cols) else 0)
+    labels = alignment_labels(torch.from_numpy(cols.frag).to(dev), torch.from_numpy(ptr).to(dev),
+                              torch.from_numpy(group_frag).to(dev), row_label, n_frag)
+    return ContribReads(cols, labels, names, list(table), dcols)

@@ -2209,43 +2209,49 @@ extern "C" int mxm_fold_logaddexp(double *acc, int64_t lda, const double *const 
 }
 
 // The pileup (observe_kernels.hpp).  Blocking: the scratch is stream-ordered memory of the call's own, and the error word
-// is read back before returning.
-extern "C" int mxm_observe_bases(const mxm_aln_columns *cols, const uint8_t *is_reverse, int32_t min_mq, int32_t min_bq,
-                                 int64_t L, uint32_t *counts, void *stream) {
-    if (cols == nullptr || cols->n_aln < 0 || L < 0 || (L > 0 && counts == nullptr))
-        return fail(-1, "mxm_observe_bases: bad arguments%s", "");
+// is read back before returning.  LABELLED: n_labels tables counts[n_labels][L][16], alignment i into table label[i]
+// (negative: not counted); otherwise one table and `label` / n_labels are not read.
+template <bool LABELLED>
+static int observe_bases_impl(const char *name, const mxm_aln_columns *cols, const uint8_t *is_reverse,
+                              const int32_t *label, int32_t n_labels, int32_t min_mq, int32_t min_bq, int64_t L,
+                              uint32_t *counts, void *stream) {
+    if (cols == nullptr || cols->n_aln < 0 || L < 0 || (L > 0 && n_labels > 0 && counts == nullptr))
+        return fail(-1, "%s: bad arguments", name);
     const int64_t n = cols->n_aln;
+    if (LABELLED && n_labels < 0) return fail(-1, "%s: n_labels < 0 (%lld)", name, n_labels);
     if (n == 0) return 0;
-    if (n > 0x7fffffffLL) return fail(-1, "mxm_observe_bases: more than 2^31 - 1 alignments%s (%lld)", "", n);
+    if (n > 0x7fffffffLL) return fail(-1, "%s: more than 2^31 - 1 alignments (%lld)", name, n);
     if (cols->ref_start == nullptr || cols->mapq == nullptr || cols->cig_ptr == nullptr || cols->cigar == nullptr ||
         cols->seq_ptr == nullptr || cols->seq == nullptr)
-        return fail(-1, "mxm_observe_bases: ref_start, mapq, cig_ptr, cigar, seq_ptr and seq are required%s", "");
+        return fail(-1, "%s: ref_start, mapq, cig_ptr, cigar, seq_ptr and seq are required", name);
+    if (LABELLED && label == nullptr) return fail(-1, "%s: label is required", name);
     hipStream_t s = (hipStream_t)stream;
-    const int64_t nb = (L + OBS_BUCKET - 1) / OBS_BUCKET;
-    // scratch: cnt[nb], cursor[nb], off[nb + 1], chunk_off[nb + 1], err, then perm[n] (int32)
-    const size_t words = (size_t)(4 * nb + 3);
+    const int64_t nb = (L + OBS_BUCKET - 1) / OBS_BUCKET;   // windows of one table
+    const int64_t nbk = LABELLED ? nb * (int64_t)n_labels : nb;
+    // scratch: cnt[nbk], cursor[nbk], off[nbk + 1], chunk_off[nbk + 1], err, then perm[n] (int32)
+    const size_t words = (size_t)(4 * nbk + 3);
     void *scratch = nullptr;
     HIP_TRY(hipMallocAsync(&scratch, words * 8 + (size_t)n * 4, s));
-    unsigned long long *cnt = static_cast<unsigned long long *>(scratch), *cursor = cnt + nb, *off = cursor + nb,
-                       *chunk_off = off + nb + 1, *err = chunk_off + nb + 1;
+    unsigned long long *cnt = static_cast<unsigned long long *>(scratch), *cursor = cnt + nbk, *off = cursor + nbk,
+                       *chunk_off = off + nbk + 1, *err = chunk_off + nbk + 1;
     int32_t *perm = reinterpret_cast<int32_t *>(err + 1);
     unsigned long long err_host = OBS_ERR_NONE;
-    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)nb * 8, s);
+    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)nbk * 8, s);
     if (e == hipSuccess) e = hipMemsetAsync(err, 0xff, 8, s);
     if (e == hipSuccess) {
         const unsigned grid_b = (unsigned)((n + OBS_BKT_PER_WG - 1) / OBS_BKT_PER_WG);
-        hipLaunchKernelGGL(observe_bucket_kernel<0>, dim3(grid_b), dim3(OBS_BKT_THREADS), 0, s, cols->ref_start, cols->mapq, n,
-                           min_mq, L, nb, cnt, perm, err);
-        hipLaunchKernelGGL(observe_scan_kernel, dim3(1), dim3(1024), 0, s, cnt, nb, off, chunk_off, cursor);
-        hipLaunchKernelGGL(observe_bucket_kernel<1>, dim3(grid_b), dim3(OBS_BKT_THREADS), 0, s, cols->ref_start, cols->mapq, n,
-                           min_mq, L, nb, cursor, perm, err);
+        hipLaunchKernelGGL((observe_bucket_kernel<LABELLED, 0>), dim3(grid_b), dim3(OBS_BKT_THREADS), 0, s,
+                           cols->ref_start, cols->mapq, label, n_labels, n, min_mq, L, nb, nbk, cnt, perm, err);
+        hipLaunchKernelGGL(observe_scan_kernel, dim3(1), dim3(1024), 0, s, cnt, nbk, off, chunk_off, cursor);
+        hipLaunchKernelGGL((observe_bucket_kernel<LABELLED, 1>), dim3(grid_b), dim3(OBS_BKT_THREADS), 0, s,
+                           cols->ref_start, cols->mapq, label, n_labels, n, min_mq, L, nb, nbk, cursor, perm, err);
         // at most one partial chunk per bucket beyond the full ones
-        const int64_t grid_c = (n + OBS_CHUNK - 1) / OBS_CHUNK + nb;
+        const int64_t grid_c = (n + OBS_CHUNK - 1) / OBS_CHUNK + nbk;
         if (grid_c > 0x7fffffffLL) e = hipErrorInvalidValue;
         else {
-            hipLaunchKernelGGL(observe_count_kernel, dim3((unsigned)grid_c), dim3(OBS_THREADS), 0, s, cols->ref_start,
-                               cols->cig_ptr, cols->cigar, cols->seq_ptr, cols->seq, cols->qual, cols->has_qual, is_reverse,
-                               min_bq, L, nb, off, chunk_off, perm, counts, err);
+            hipLaunchKernelGGL(observe_count_kernel<LABELLED>, dim3((unsigned)grid_c), dim3(OBS_THREADS), 0, s,
+                               cols->ref_start, cols->cig_ptr, cols->cigar, cols->seq_ptr, cols->seq, cols->qual,
+                               cols->has_qual, is_reverse, min_bq, L, nb, nbk, off, chunk_off, perm, counts, err);
             e = hipGetLastError();
         }
         if (e == hipSuccess) e = hipMemcpyAsync(&err_host, err, 8, hipMemcpyDeviceToHost, s);
@@ -2257,10 +2263,24 @@ extern "C" int mxm_observe_bases(const mxm_aln_columns *cols, const uint8_t *is_
     if (err_host != OBS_ERR_NONE) {
         const long long i = (long long)(err_host >> 2);
         switch ((int)(err_host & 3)) {
-            case 1: return fail(-4, "mxm_observe_bases: the CIGAR of alignment %s%lld runs past its sequence", "", i);
-            case 2: return fail(-4, "mxm_observe_bases: the CIGAR of alignment %s%lld holds an unknown operation", "", i);
-            default: return fail(-1, "mxm_observe_bases: alignment %s%lld reaches past the table (L = %lld)", "", i, L);
+            case 0: return fail(-1, "%s: alignment %lld has a label >= n_labels (%lld)", name, i, n_labels);
+            case 1: return fail(-4, "%s: the CIGAR of alignment %lld runs past its sequence", name, i);
+            case 2: return fail(-4, "%s: the CIGAR of alignment %lld holds an unknown operation", name, i);
+            default: return fail(-1, "%s: alignment %lld reaches past the table (L = %lld)", name, i, L);
         }
     }
     return 0;
+}
+
+extern "C" int mxm_observe_bases(const mxm_aln_columns *cols, const uint8_t *is_reverse, int32_t min_mq, int32_t min_bq,
+                                 int64_t L, uint32_t *counts, void *stream) {
+    return observe_bases_impl<false>("mxm_observe_bases", cols, is_reverse, nullptr, 1, min_mq, min_bq, L, counts,
+                                     stream);
+}
+
+extern "C" int mxm_observe_bases_labelled(const mxm_aln_columns *cols, const uint8_t *is_reverse, const int32_t *label,
+                                          int32_t n_labels, int32_t min_mq, int32_t min_bq, int64_t L, uint32_t *counts,
+                                          void *stream) {
+    return observe_bases_impl<true>("mxm_observe_bases_labelled", cols, is_reverse, label, n_labels, min_mq, min_bq, L,
+                                    counts, stream);
 }

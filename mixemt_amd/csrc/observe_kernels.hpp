@@ -21,6 +21,12 @@
 //               atomics covering 4 positions x 16 bins = 256 contiguous bytes
 // Errors (the first alignment in index order wins, atomicMin): a CIGAR that runs past its sequence or holds an
 // unknown operation (-4, as mxm_aln_encode), a reference position >= L (-1: the table is too short).
+//
+// Labelled form (LABELLED = true, mxm_observe_bases_labelled): alignment i with label[i] in [0, n_labels) is counted into
+// table counts[label[i]][L][16]; label[i] < 0 is not counted, label[i] >= n_labels is an error (-1).  The bucket key
+// widens to label * nb + ref_start / OBS_BUCKET over n_labels * nb buckets (nb = windows of one table), so a count
+// workgroup still holds ONE window of ONE table: the key gives the label (the table's base) and the window.  With
+// LABELLED = false the key is the window and the kernels are the unlabelled pileup's.
 #ifndef MIXEMT_OBSERVE_KERNELS_HPP
 #define MIXEMT_OBSERVE_KERNELS_HPP
 
@@ -33,7 +39,8 @@
 #define OBS_BKT_PER_WG 4096        // alignments per bucket workgroup
 #define OBS_LDS_BUCKETS 2048       // buckets an LDS histogram of step 1 holds (L up to 1 M); more: global atomics
 
-// error word: (alignment index << 2) | kind, kind 1 = CIGAR past the sequence, 2 = unknown operation, 3 = position >= L
+// error word: (alignment index << 2) | kind, kind 1 = CIGAR past the sequence, 2 = unknown operation, 3 = position >= L,
+// 0 = label >= n_labels (labelled form only)
 #define OBS_ERR_NONE 0xffffffffffffffffull
 
 __device__ __forceinline__ bool obs_counts(const int64_t *ref_start, const int32_t *mapq, int32_t min_mq, int64_t i) {
@@ -44,12 +51,40 @@ __device__ __forceinline__ void obs_error(unsigned long long *err, int64_t i, un
     atomicMin(err, ((unsigned long long)i << 2) | kind);
 }
 
+// The bucket of alignment i, or -1 when it is not counted (LABELLED: a negative label, or an error of kind 0, which
+// mode 0 records).  nb: windows of one table.
+template <bool LABELLED, int MODE>
+__device__ __forceinline__ int64_t obs_bucket_of(const int64_t *ref_start, const int32_t *mapq, const int32_t *label,
+                                                 int32_t n_labels, int32_t min_mq, int64_t L, int64_t nb, int64_t i,
+                                                 unsigned long long *err) {
+    int64_t lab = 0;
+    if (LABELLED) {
+        lab = label[i];
+        if (lab >= n_labels) {
+            if (MODE == 0) obs_error(err, i, 0);
+            return -1;
+        }
+        if (lab < 0) return -1;
+    }
+    if (!obs_counts(ref_start, mapq, min_mq, i)) return -1;
+    const int64_t r = ref_start[i];
+    if (r >= L) {
+        if (MODE == 0) obs_error(err, i, 3);
+        return -1;
+    }
+    return (LABELLED ? lab * nb : 0) + r / OBS_BUCKET;
+}
+
 // step 1a / 1b: mode 0 counts the alignments of each bucket into cnt[b]; mode 1 scatters their indices into perm at
-// cursor[b] (cursor = the buckets' exclusive offsets, advanced by the reservations)
-template <int MODE>
+// cursor[b] (cursor = the buckets' exclusive offsets, advanced by the reservations).  nbk: buckets in all
+// (n_labels * nb labelled, nb otherwise).
+template <bool LABELLED, int MODE>
 __global__ __launch_bounds__(OBS_BKT_THREADS) void observe_bucket_kernel(const int64_t *__restrict__ ref_start,
-                                                                         const int32_t *__restrict__ mapq, int64_t n_aln,
+                                                                         const int32_t *__restrict__ mapq,
+                                                                         const int32_t *__restrict__ label,
+                                                                         int32_t n_labels, int64_t n_aln,
                                                                          int32_t min_mq, int64_t L, int64_t nb,
+                                                                         int64_t nbk,
                                                                          unsigned long long *cnt_or_cursor,
                                                                          int32_t *__restrict__ perm,
                                                                          unsigned long long *err) {
@@ -57,20 +92,15 @@ __global__ __launch_bounds__(OBS_BKT_THREADS) void observe_bucket_kernel(const i
     __shared__ unsigned long long base[OBS_LDS_BUCKETS];
     const int64_t lo = (int64_t)blockIdx.x * OBS_BKT_PER_WG;
     const int64_t hi = min(n_aln, lo + (int64_t)OBS_BKT_PER_WG);
-    const bool in_lds = nb <= OBS_LDS_BUCKETS;
+    const bool in_lds = nbk <= OBS_LDS_BUCKETS;
     if (in_lds) {
-        for (int64_t b = threadIdx.x; b < nb; b += blockDim.x) h[b] = 0;
+        for (int64_t b = threadIdx.x; b < nbk; b += blockDim.x) h[b] = 0;
         __syncthreads();
     }
     // pass over this workgroup's alignments: per-workgroup counts
     for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        if (!obs_counts(ref_start, mapq, min_mq, i)) continue;
-        const int64_t r = ref_start[i];
-        if (r >= L) {
-            if (MODE == 0) obs_error(err, i, 3);
-            continue;
-        }
-        const int64_t b = r / OBS_BUCKET;
+        const int64_t b = obs_bucket_of<LABELLED, MODE>(ref_start, mapq, label, n_labels, min_mq, L, nb, i, err);
+        if (b < 0) continue;
         if (in_lds) {
             atomicAdd(&h[b], 1u);
         } else if (MODE == 0) {
@@ -82,21 +112,19 @@ __global__ __launch_bounds__(OBS_BKT_THREADS) void observe_bucket_kernel(const i
     if (!in_lds) return;
     __syncthreads();
     if (MODE == 0) {
-        for (int64_t b = threadIdx.x; b < nb; b += blockDim.x)
+        for (int64_t b = threadIdx.x; b < nbk; b += blockDim.x)
             if (h[b]) atomicAdd(&cnt_or_cursor[b], (unsigned long long)h[b]);
         return;
     }
     // reserve this workgroup's slots in every bucket it has alignments in, then hand them out
-    for (int64_t b = threadIdx.x; b < nb; b += blockDim.x) {
+    for (int64_t b = threadIdx.x; b < nbk; b += blockDim.x) {
         if (h[b]) base[b] = atomicAdd(&cnt_or_cursor[b], (unsigned long long)h[b]);
         h[b] = 0;
     }
     __syncthreads();
     for (int64_t i = lo + threadIdx.x; i < hi; i += blockDim.x) {
-        if (!obs_counts(ref_start, mapq, min_mq, i)) continue;
-        const int64_t r = ref_start[i];
-        if (r >= L) continue;
-        const int64_t b = r / OBS_BUCKET;
+        const int64_t b = obs_bucket_of<LABELLED, 1>(ref_start, mapq, label, n_labels, min_mq, L, nb, i, err);
+        if (b < 0) continue;
         perm[base[b] + atomicAdd(&h[b], 1u)] = (int32_t)i;
     }
 }
@@ -155,26 +183,30 @@ __device__ __forceinline__ int obs_base_bin(uint8_t b) {
     }
 }
 
-// step 2: grid = an upper bound of the chunk count (workgroups past chunk_off[nb] leave at once)
+// step 2: grid = an upper bound of the chunk count (workgroups past chunk_off[nbk] leave at once).  nb: windows of one
+// table, nbk: buckets in all (see observe_bucket_kernel).
+template <bool LABELLED>
 __global__ __launch_bounds__(OBS_THREADS) void observe_count_kernel(
     const int64_t *__restrict__ ref_start, const int64_t *__restrict__ cig_ptr, const uint32_t *__restrict__ cigar,
     const int64_t *__restrict__ seq_ptr, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ qual,
     const uint8_t *__restrict__ has_qual, const uint8_t *__restrict__ is_reverse, int32_t min_bq, int64_t L, int64_t nb,
-    const unsigned long long *__restrict__ off, const unsigned long long *__restrict__ chunk_off,
-    const int32_t *__restrict__ perm, uint32_t *__restrict__ counts, unsigned long long *err) {
+    int64_t nbk, const unsigned long long *__restrict__ off, const unsigned long long *__restrict__ chunk_off,
+    const int32_t *__restrict__ perm, uint32_t *__restrict__ counts_all, unsigned long long *err) {
     __shared__ uint32_t hist[OBS_NBIN * OBS_WIN];
     const unsigned long long g = blockIdx.x;
-    if (g >= chunk_off[nb]) return;
-    // the bucket holding chunk g: the last b with chunk_off[b] <= g (buckets without alignments have no chunk)
-    int64_t lo_b = 0, hi_b = nb;                             // chunk_off[lo_b] <= g < chunk_off[hi_b]
+    if (g >= chunk_off[nbk]) return;
+    // the bucket holding chunk g: the last key with chunk_off[key] <= g (buckets without alignments have no chunk)
+    int64_t lo_b = 0, hi_b = nbk;                            // chunk_off[lo_b] <= g < chunk_off[hi_b]
     while (hi_b - lo_b > 1) {
         const int64_t mid = (lo_b + hi_b) >> 1;
         if (chunk_off[mid] <= g) lo_b = mid;
         else hi_b = mid;
     }
-    const int64_t b = lo_b;
-    const unsigned long long a0 = off[b] + (g - chunk_off[b]) * OBS_CHUNK;
-    const unsigned long long a1 = min(off[b + 1], a0 + (unsigned long long)OBS_CHUNK);
+    const int64_t key = lo_b;
+    const unsigned long long a0 = off[key] + (g - chunk_off[key]) * OBS_CHUNK;
+    const unsigned long long a1 = min(off[key + 1], a0 + (unsigned long long)OBS_CHUNK);
+    const int64_t b = LABELLED ? key % nb : key;             // the window within its table
+    uint32_t *__restrict__ counts = LABELLED ? counts_all + (key / nb) * L * 16 : counts_all;
     const int64_t w0 = b * OBS_BUCKET;                       // window [w0, w0 + OBS_WIN)
     for (int k = threadIdx.x; k < OBS_NBIN * OBS_WIN; k += blockDim.x) hist[k] = 0;
     __syncthreads();

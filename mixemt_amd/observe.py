@@ -5,6 +5,7 @@ The pileup of mixemt's variant check -- observe.ObservedBases (the reference's m
     obs.counts                  uint32 [L][16]: per position the bins of mxm_observe_bases (BINS below)
     obs.obs_at(pos, base=None, stranded=False), obs.total_obs(pos)            the reference's queries (observe.py:88-145)
     obs.obs_tab[pos]            a Counter of the position's observations, as the reference's attribute holds them
+    count_bases_labelled(dcols, label, counts)     one table per label in one call (stats.write_statistics' tables)
 
 The reference walks pysam's get_aligned_pairs(matches_only=False) one tuple at a time (observe.py:56-86); here one
 library call (mxm_observe_bases, csrc/observe_kernels.hpp) counts every alignment's bases and gaps into the table.
@@ -98,6 +99,26 @@ def count_bases(dcols, counts, min_mq=30, min_bq=30):
     rev = 0 if dcols.is_reverse is None else dcols.is_reverse.data_ptr()
     _lib.check(lib.mxm_observe_bases(ctypes.byref(st), rev, int(min_mq), int(min_bq), int(counts.shape[0]),
                                      counts.data_ptr(), current_stream()), "mxm_observe_bases")
+    return counts
+
+
+def count_bases_labelled(dcols, label, counts, min_mq=30, min_bq=30):
+    """
+    mxm_observe_bases_labelled: add each label's pileup to its table in ONE call -- alignment i with label[i] in
+    [0, n_labels) into counts[label[i]], label[i] < 0 not counted.  label: int32 device tensor [n_aln]; counts: a zeroed
+    or earlier-filled contiguous int32 device tensor [n_labels][L][16].  Raises ValueError with the library's message
+    (as count_bases, and for a label >= n_labels).
+    """
+    if counts.dim() != 3 or counts.shape[2] != 16 or counts.dtype != torch.int32 or not counts.is_contiguous():
+        raise ValueError("counts must be a contiguous int32 [n_labels][L][16] device tensor")
+    if label.dtype != torch.int32 or label.dim() != 1 or not label.is_contiguous() or label.numel() < dcols.n_aln:
+        raise ValueError("label must be a contiguous int32 device tensor with one entry per alignment")
+    lib = _lib.load()
+    st = dcols.struct()
+    rev = 0 if dcols.is_reverse is None else dcols.is_reverse.data_ptr()
+    _lib.check(lib.mxm_observe_bases_labelled(ctypes.byref(st), rev, label.data_ptr(), int(counts.shape[0]), int(min_mq),
+                                              int(min_bq), int(counts.shape[1]), counts.data_ptr(), current_stream()),
+               "mxm_observe_bases_labelled")
     return counts
 
 

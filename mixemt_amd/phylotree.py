@@ -203,6 +203,23 @@ class Phylotree(object):
             ancestral.pop(pos_from_var(var), None)
         return list(ancestral.items())
 
+    def polymorphic_sites(self, haps, ref=None):
+        """
+        Sorted 0-based sites expected to be polymorphic in a sample of the haplogroups `haps` (reference:
+        phylotree.py:276-315): among the variants of `haps` whose derived base differs from `ref` (default: refseq), a
+        site is polymorphic when fewer than len(haps) such variants fall on it or their derived bases differ.
+        """
+        if ref is None:
+            ref = self.refseq
+        var_tab = collections.defaultdict(list)
+        for hap in haps:
+            for var in self.hap_var[hap]:
+                pos = pos_from_var(var)
+                if der_allele(var) != ref[pos]:
+                    var_tab[pos].append(der_allele(var))
+        return [pos for pos in sorted(var_tab)
+                if len(var_tab[pos]) < len(haps) or any(der != var_tab[pos][0] for der in var_tab[pos])]
+
     def add_custom_hap(self, hap_id, variants):
         """Reference: phylotree.py:231-251 (ValueError on a name clash)."""
         if hap_id in self.hap_var:
@@ -282,23 +299,32 @@ def load_build16(refseq=None, anon_haps=True, rm_unstable=False, rm_backmut=Fals
                          rm_backmut=rm_backmut)
 
 
+# The 9-haplogroup toy tree used throughout the reference's tests (em_test.py:78-88); data, restated here for the
+# parity tests.
+#            I
+#           / \
+#          /   H
+#         /   / \
+#        A   F   G
+#           / \ / \
+#          B  C D  E
+_EXAMPLE_ROWS = ("I, A1G ,,",
+                 ",H, A3T A5T ,,",
+                 ",,F, A6T ,,",
+                 ",,,B, A8T ,,",
+                 ",,,C, T5A ,,",
+                 ",,G, A7T ,,",
+                 ",,,D, A9T ,,",
+                 ",,,E, A4T ,,",
+                 ",A, A2T A4T ,,")
+
+
 def example():
     """The 9-haplogroup toy tree used throughout the reference's tests
-    (em_test.py:78-88); data, restated here for the parity tests."""
-    #            I
-    #           / \
-    #          /   H
-    #         /   / \
-    #        A   F   G
-    #           / \ / \
-    #          B  C D  E
-    rows = ["I, A1G ,,",
-            ",H, A3T A5T ,,",
-            ",,F, A6T ,,",
-            ",,,B, A8T ,,",
-            ",,,C, T5A ,,",
-            ",,G, A7T ,,",
-            ",,,D, A9T ,,",
-            ",,,E, A4T ,,",
-            ",A, A2T A4T ,,"]
-    return Phylotree(rows)
+    (em_test.py:78-88)."""
+    return Phylotree(list(_EXAMPLE_ROWS))
+
+
+def example_rows():
+    """The CSV lines of example()'s tree."""
+    return list(_EXAMPLE_ROWS)

@@ -39,6 +39,11 @@ Fixtures (SURVEY.md section 8 c):
         hand-made alignments (D, N, an H clip, non-ACGTN bases, an unplaced one, mapq / bq at the 29 / 30 edges) --
         tests/_pileup_aln.py objects --, its process_reads -> build_em_matrix -> run_em, get_contributors with the
         check on under four argument sets, write_base_obs bytes and get_ancestral of the candidates
+    g17 mixemt's `-t` output: g16's alignments (make_g16_alignments, same seeds) through the reference's own pipeline on
+        (get_contributors with the default check, reduce_em_matrix, refinement run_em, update_contribs), then its
+        assemble.assign_reads over the alignment objects, stats.report_contributors and stats.write_statistics in
+        bin/mixemt's order (bin/mixemt:296-338), for three cases: default, every row unassigned (a huge min_fold),
+        one contributor (a min_reads that leaves one candidate)
 """
 
 import argparse
@@ -255,6 +260,17 @@ def make_g16_alignments(refseq, tables, n_frag=4000):
     every = [(alns + extra)[k] for k in order]
     cols = AlignmentColumns.from_alignments(every)
     return cols, from_columns(cols)
+
+
+G17_REFINE_SEED = 17   # numpy.random seed in front of g17's refinement run_em
+
+
+def _columns_sha(cols):
+    h = hashlib.sha256()
+    for name in ("ref_start", "mapq", "frag", "cig_ptr", "cigar", "seq_ptr", "seq", "qual", "has_qual", "is_reverse"):
+        h.update(numpy.ascontiguousarray(getattr(cols, name)).tobytes())
+    h.update("\n".join(cols.names).encode())
+    return h.hexdigest()
 
 
 def main():
@@ -741,6 +757,91 @@ def main():
              signatures=numpy.array("\n".join(rows)), weights=wts.astype(numpy.int64),
              base_obs=numpy.array(buf.getvalue()), verbose_text=numpy.array(verbose_text),
              ancestral=numpy.array(json.dumps(ancestral)), **out)
+
+    if want("g17"):
+        for name in ("pysam", "Bio", "Bio.Seq", "Bio.SeqRecord", "Bio.SeqIO"):
+            sys.modules.setdefault(name, types.ModuleType(name))
+        sys.modules["Bio"].SeqIO = sys.modules["Bio.SeqIO"]
+        sys.modules["Bio.Seq"].Seq = object
+        sys.modules["Bio.SeqRecord"].SeqRecord = object
+        import collections
+        import json
+        import tempfile
+        import mixemt.assemble
+        import mixemt.observe
+        import mixemt.stats
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from _pileup_aln import PileupBam
+        cols, alns = make_g16_alignments(refseq, tables)
+        t0 = time.time()
+        obs = ref.observe.ObservedBases(alns, mapq=30, baseq=30)
+        read_obs = ref.preprocess.process_reads(alns, phy.get_variant_pos(), 30, 30)
+        read_sigs = ref.preprocess.reduce_reads(read_obs)
+        read_sigs.pop("", None)
+        rows = sorted(read_sigs)
+        reads = [read_sigs[r] for r in rows]
+        wts = numpy.array([len(r) for r in reads])
+        mat = ref.preprocess.build_em_matrix(refseq, phy, rows, haps, quiet)
+        props, mix, iters, inits = ref_run_em(ref, mat, wts, G16_EM_SEED)
+        print("g17: pileup + matrix %d x %d + run_em in %.0f s" % (mat.shape[0], mat.shape[1], time.time() - t0), flush=True)
+        votes = collections.Counter()
+        for r, h in enumerate(numpy.argmax(mix, 1)):
+            votes[int(h)] += int(wts[r])
+        top = sorted(votes.values(), reverse=True)
+        one_min_reads = top[1] + 1                    # leaves the most voted candidate alone
+        base = dict(min_reads=G16_MIN_READS, contributors=None, var_check=True, min_fold=2.0, min_var_reads=3,
+                    frac_var_reads=0.02, var_fraction=0.5, var_count=None, min_mq=30, min_bq=30)
+        cases = [("default", {}), ("unassigned", {"min_fold": 1e300}), ("one", {"min_reads": one_min_reads})]
+        names_of = [cols.names[int(f)] for f in cols.frag]
+        out = {}
+        for label, kw in cases:
+            a = ns(**dict(base, **kw))
+            contribs = ref.assemble.get_contributors(phy, obs, haps, wts, (props, mix), a)
+            sub, sub_haps = ref.preprocess.reduce_em_matrix(mat, haps, contribs)
+            numpy.random.seed(G17_REFINE_SEED)
+            res = ref.em.run_em(sub, wts, a)
+            contribs = ref.assemble.update_contribs(contribs, res, sub_haps)
+            contrib_reads = ref.assemble.assign_reads(PileupBam(alns), contribs, res, sub_haps, reads, a)
+            report = io.StringIO()
+            ref.stats.report_contributors(report, contribs, contrib_reads)
+            with tempfile.TemporaryDirectory() as tmp:
+                a.stats_prefix = os.path.join(tmp, "run")
+                ref.stats.write_statistics(phy, obs, contribs, contrib_reads, a)
+                with open(a.stats_prefix + ".pos.tab") as fin:
+                    pos_tab = fin.read()
+                with open(a.stats_prefix + ".obs.tab") as fin:
+                    obs_tab = fin.read()
+            keys = sorted(contrib_reads)
+            key_of = {}
+            for k, key in enumerate(keys):
+                for aln in contrib_reads[key]:
+                    key_of[id(aln)] = k
+            aln_key = numpy.array([key_of.get(id(aln), -1) for aln in alns], dtype=numpy.int32)
+            n_un = len(contrib_reads.get("unassigned", []))
+            print("g17 %-10s: %d contributors, keys %s, %d alignments unassigned, %d in no table"
+                  % (label, len(contribs), keys, n_un, int((aln_key < 0).sum())), flush=True)
+            if label == "default":
+                assert len(contribs) >= 2 and n_un > 0
+            elif label == "unassigned":
+                assert len(contribs) >= 2 and all(len(contrib_reads[c[0]]) == 0 for c in contribs)
+            else:
+                assert len(contribs) == 1 and "unassigned" not in contrib_reads
+            out[label + "_contribs"] = numpy.array("\n".join("%s\t%s\t%r" % (c[0], c[1], float(c[2])) for c in contribs))
+            out[label + "_args"] = numpy.array(json.dumps(kw))
+            out[label + "_report"] = numpy.array(report.getvalue())
+            out[label + "_pos_tab"] = numpy.array(pos_tab)
+            out[label + "_obs_tab"] = numpy.array(obs_tab)
+            out[label + "_keys"] = numpy.array("\n".join(keys))
+            out[label + "_aln_key"] = aln_key
+        # polymorphic_sites (phylotree.py:276-315) on the 9-haplogroup toy tree, reference all 'A' and one other
+        toy = ref.phylotree.Phylotree(my_phy.example_rows())
+        poly = {}
+        for ref_seq in ("A" * 10, "AGTAAAAAAA"):
+            for hs in (["A"], ["F", "G"], ["A", "C"], ["B", "C", "D", "E"], ["I"], ["H", "B", "E"], ["C", "C"]):
+                poly["%s|%s" % (ref_seq, ",".join(hs))] = toy.polymorphic_sites(hs, ref_seq)
+        out["toy_polymorphic"] = numpy.array(json.dumps(poly))
+        save("g17_stats", seeds=numpy.array([G16_SEED, G16_EM_SEED, G17_REFINE_SEED]),
+             columns_sha256=numpy.array(_columns_sha(cols)), **out)
 
     if want("g7"):
         cols = list(range(0, 5400, 54))

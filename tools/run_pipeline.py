@@ -7,7 +7,7 @@ synthetic reads, device-resident end to end:
     -> refinement EM on the contributor columns -> read assignment -> contributor table
 
     python tools/run_pipeline.py [--reads N] [--seed S] [--multi M] [--dense [--storage f64|f32|coded|auto]] [--alignments]
-                                 [--pairs | --read-len L] [--var-check [-R N] [-F F] [-f F] [-n N]]
+                                 [--pairs | --read-len L] [--var-check [-R N] [-F F] [-f F] [-n N]] [--stats PREFIX]
 
 --alignments (round 5): start one step earlier, from ALIGNMENTS -- N synthetic fragments (synth-aln-v1: mates, indels,
 clips, low qualities, duplicates) as columns -> the library's batched front end (alignments.encode_alignments =
@@ -17,6 +17,11 @@ groups, and the stage is timed beside the others.
 --var-check (with --alignments, opt-in): the candidates pass the reference's variant check (assemble.py:126-208; on by
 default in bin/mixemt) over a pileup of the same columns (observe.observe_bases) before the refinement EM; -R / -F / -f /
 -n are bin/mixemt's knobs at its defaults.  Without it the output is what it was.
+
+--stats PREFIX (with --alignments, opt-in): bin/mixemt's -t PREFIX (bin/mixemt:333-338): the alignments go to their
+contributors (assign.assign_reads: one label per alignment on the device), the contributor table is the reference's
+report_contributors (its Reads column counts alignments), and stats.write_statistics writes PREFIX.pos.tab and
+PREFIX.obs.tab (every contributor's pileup from one labelled call).  Without it the output is what it was.
 
 Default (round 3): the build leaves the matrix as row-dictionary records -- no dense matrix, no posterior matrix; the
 contributors, the vote table and the reduced matrix for the refinement come from the records.  --dense takes the
@@ -59,6 +64,8 @@ def main():
     ap.add_argument("-F", "--var-fraction-min-reads", dest="frac_var_reads", type=float, default=0.02)
     ap.add_argument("-f", "--var-fraction", dest="var_fraction", type=float, default=0.5)
     ap.add_argument("-n", "--var-count", dest="var_count", type=int, default=None)
+    ap.add_argument("--stats", dest="stats_prefix", default=None, metavar="PREFIX",
+                    help="with --alignments: write mixemt's -t tables PREFIX.pos.tab and PREFIX.obs.tab (stats.py:138-171)")
     ap.add_argument("--threads", type=int, default=0, help="with --alignments: host threads of the encoder (0 = its default)")
     ap.add_argument("--storage", default="auto", choices=["f64", "f32", "coded", "auto"],
                     help="with --dense: form of the matrix the EM loop streams (EmPlan): coded = lossless row dictionaries, "
@@ -67,6 +74,8 @@ def main():
     opts.records = not opts.dense
     if opts.var_check and not opts.alignments:
         ap.error("--var-check needs --alignments (the pileup is made from the alignments)")
+    if opts.stats_prefix and not opts.alignments:
+        ap.error("--stats needs --alignments (the tables are pileups of the alignments)")
     args = argparse.Namespace(init_alpha=1.0, tolerance=1e-4, max_iter=10000, n_multi=opts.multi,
                               verbose=True, min_reads=10, min_fold=2.0, storage=opts.storage)
     numpy.random.seed(opts.seed)                       # bin/mixemt:507-508
@@ -197,7 +206,7 @@ def main():
     torch.cuda.synchronize()
     sys.stderr.write("contributors from read votes: %.1f ms\n" % ((time.perf_counter() - t0) * 1e3))
     contribs = sorted(([haps[c], props[c]] for c in cons), key=lambda c: c[1], reverse=True)
-    if opts.var_check:
+    if opts.var_check or opts.stats_prefix:
         from mixemt_amd import observe
         t0 = time.perf_counter()
         L = observe.pileup_length(cols, 30, len(refseq))
@@ -209,7 +218,9 @@ def main():
         t2 = time.perf_counter()
         sys.stderr.write("pileup of %d alignments (observe_bases): %.1f ms on the device + table back, upload of the "
                          "columns %.1f ms apart\n" % (len(cols), (t2 - t1) * 1e3, dcols.upload_s * 1e3))
-        del dcols
+        if not opts.stats_prefix:
+            del dcols
+    if opts.var_check:
         chk = argparse.Namespace(min_var_reads=opts.min_var_reads, frac_var_reads=opts.frac_var_reads,
                                  var_fraction=opts.var_fraction, var_count=opts.var_count, verbose=True)
         n_cand = len(contribs)
@@ -238,6 +249,24 @@ def main():
                      % (opts.reads, (time.perf_counter() - t0) * 1e3))
 
     sys.stderr.write("tables -> read assignment, all stages: %.1f ms\n" % ((time.perf_counter() - t_all) * 1e3))
+    if opts.stats_prefix:
+        from mixemt_amd import stats
+        t0 = time.perf_counter()
+        contrib_reads = assign.assign_reads(cols, contribs, results, sub_haps, reads, args, dcols)
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        stats.report_contributors(sys.stdout, contribs, contrib_reads)
+        sys.stdout.flush()
+        st = argparse.Namespace(stats_prefix=opts.stats_prefix, min_mq=30, min_bq=30, min_var_reads=opts.min_var_reads,
+                                frac_var_reads=opts.frac_var_reads)
+        t2 = time.perf_counter()
+        stats.write_statistics(phy, base_obs, contribs, contrib_reads, st)
+        t3 = time.perf_counter()
+        sys.stderr.write("-t output: alignment labels (assign_reads) %.1f ms, write_statistics (one labelled pileup of %d "
+                         "tables + both files) %.1f ms: %s.pos.tab, %s.obs.tab\n"
+                         % ((t1 - t0) * 1e3, len(contrib_reads.names), (t3 - t2) * 1e3, opts.stats_prefix,
+                            opts.stats_prefix))
+        return 0
     print("hap#   Haplogroup      Contribution   Reads")
     print("-------------------------------------------")
     for hap_id, group, prop in contribs:
