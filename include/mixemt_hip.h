@@ -56,8 +56,10 @@ extern "C" {
  * mxm_em_iter_coded / mxm_em_loop_coded take full tiles of three through em_iter_quad_batched_kernel),
  * mxm_quad_loop_min_rows;
  * 601: mxm_observe_bases (the pileup of mixemt's variant check);
- * 602: mxm_observe_bases_labelled (one pileup per label: the per-contributor tables of mixemt's `-t` output). */
-#define MXM_VERSION 602
+ * 602: mxm_observe_bases_labelled (one pileup per label: the per-contributor tables of mixemt's `-t` output);
+ * 603: mxm_consensus, mxm_new_variants, mxm_first_observed, mxm_extend_assign (mixemt's `-b` consensus and `-x`
+ * assembly extension over labelled pileups). */
+#define MXM_VERSION 603
 
 /* per-restart loop state, written by mxm_m_finalize (24 bytes); allocate it ZEROED */
 typedef struct mxm_em_state {
@@ -598,6 +600,66 @@ int  mxm_observe_bases(const mxm_aln_columns *cols, const uint8_t *is_reverse, i
 int  mxm_observe_bases_labelled(const mxm_aln_columns *cols, const uint8_t *is_reverse, const int32_t *label,
                                 int32_t n_labels, int32_t min_mq, int32_t min_bq, int64_t L, uint32_t *counts,
                                 void *stream);
+
+/*
+ * The assembly stage over labelled pileups (assemble.py:431-585).  Integer work throughout: every result is the same
+ * bits for any alignment order.  Counters (n_tied, n_new, n_moved: DEVICE uint32) are ADDED to; zero them first.
+ *
+ * mxm_consensus -- call_consensus' consensus_base (assemble.py:444-459) for every position of every table:
+ * counts[n_labels][L][16] (the tables of mxm_observe_bases_labelled, 16-byte aligned) -> cons[n_labels][ref_len] uint8
+ * characters.  Strands are folded; N observations are ignored; total = A + C + G + T + other + gap (gaps and `other`
+ * count towards the coverage and can be the consensus: '-' and 'X', the library's stand-in for a character other than
+ * ACGTN).  total < min_cov (or no observation) -> 'N'; strict: the largest count must equal total, else 'N'; not strict:
+ * the base with the largest count.  tied[n_labels][ref_len] (nullable): 0, or -- not strict, several bases sharing the
+ * largest count -- the mask of their folded bins (bit 0-3 ACGT, 5 other, 6 gap); cons then holds the first of them in
+ * that order until mxm_first_observed puts the reference's choice there.  n_tied (nullable): + the tied positions.
+ * Positions >= L have no observations.  The "" of a contributor WITHOUT alignments (assemble.py:460-462) is the host's.
+ * Enqueues on `stream`.  Returns 0, -1, -2.
+ */
+int  mxm_consensus(const uint32_t *counts, int32_t n_labels, int64_t L, int64_t ref_len, int64_t min_cov, int32_t strict,
+                   uint8_t *cons, uint8_t *tied, uint32_t *n_tied, void *stream);
+
+/*
+ * mxm_new_variants -- find_new_variants (assemble.py:469-501) over the strict consensus rows that take part:
+ * rows[n_use] (HOST int32: rows of cons[n_rows][ld], ld >= ref_len).  newvar[ref_len] (DEVICE): one 32-bit word per
+ * position holding four int8 owners (byte 0-3: A C G T; -1 none), owner k = rows[k].  A position is skipped (all -1)
+ * when any participating consensus is 'N', '-' or 'X' there (an 'X' cannot be looked up by a read's real character);
+ * otherwise contributor k owns (pos, its base) when no other participating consensus has that base there -- with ONE
+ * participant every called position is its own.  n_new: + the (position, base) entries.  More than 127 participants:
+ * -1.  Enqueues on `stream`.
+ */
+int  mxm_new_variants(const uint8_t *cons, int64_t ld, int32_t n_rows, const int32_t *rows, int32_t n_use, int64_t ref_len,
+                      uint32_t *newvar, uint32_t *n_new, void *stream);
+
+/*
+ * mxm_first_observed -- the tie rule of the non-strict consensus: Counter.most_common(1) (assemble.py:455) returns,
+ * among equal counts, the base observed FIRST walking the contributor's alignment list, which holds assign_reads'
+ * alignments in file order followed by what each extension round appended, each batch in file order: the order key of
+ * alignment i is (joined[i], i) (joined DEVICE int32[n_aln], nullable = all 0).  cols as mxm_observe_bases (device
+ * pointers); label[i] in [0, n_labels) names the table, < 0 none.  Walks the alignments the pileup counts (same CIGAR
+ * walk and filters), keeps the smallest key per (table, tied position, folded bin) and writes the bin with the smallest
+ * one into cons[n_labels][ref_len] where tied[.] is set; untied positions cost no atomic.  HOST, blocking (scratch of
+ * n_labels * ref_len * 64 bytes, the size of the counts tables).  Returns 0, -1 (a label >= n_labels), -2, -4 (CIGAR).
+ */
+int  mxm_first_observed(const mxm_aln_columns *cols, const int32_t *label, const int32_t *joined, int32_t n_labels,
+                        int32_t min_mq, int32_t min_bq, int64_t ref_len, const uint8_t *tied, uint8_t *cons, void *stream);
+
+/*
+ * mxm_extend_assign -- assign_reads_from_new_vars (assemble.py:504-546).  cols as mxm_observe_bases, with frag[n_aln]
+ * (DEVICE int64, the query name) and n_frag.  (1) Every alignment with label == unassigned, mapq >= min_mq and a place
+ * is walked (M / = / X only: get_aligned_pairs(matches_only=True)); a base counts when the alignment has no qualities
+ * or its quality is >= min_bq; its upper-cased character is looked up in newvar[ref_len] (staged in LDS up to 160 KiB,
+ * read from global memory beyond), and the owners found are folded into frag_state[n_frag] (DEVICE int32 scratch, reset
+ * here): -1 none, k one owner, -2 several -- a function of the SET of owners, whatever the order.  (2) Every alignment
+ * with label == unassigned -- below min_mq too, as the reference's move loop -- whose fragment has ONE owner k gets
+ * label rows[k] (HOST int32[n_use]) and joined = round; moved_owner[n_aln] (nullable) = k or -1 (the labels of an
+ * additive pileup of what moved); n_moved: + the alignments moved.  Alignments with another label are never touched.
+ * HOST, blocking.  Returns 0, -1 (a fragment index outside [0, n_frag)), -2, -4 (CIGAR), naming the first alignment.
+ */
+int  mxm_extend_assign(const mxm_aln_columns *cols, int32_t *label, int32_t *joined, int32_t unassigned, int32_t n_rows,
+                       const int32_t *rows, int32_t n_use, int32_t round, int32_t min_mq, int32_t min_bq,
+                       const uint32_t *newvar, int64_t ref_len, int32_t *frag_state, int32_t *moved_owner,
+                       uint32_t *n_moved, void *stream);
 
 /*
  * One-shot exchange of the M-step sums between the ranks of a row-sharded loop -- OPTIONAL, instead of the all-reduce

@@ -150,6 +150,12 @@ SIGNATURES = {
     "mxm_observe_bases": (ctypes.c_int, [ctypes.POINTER(AlnColumns), c_ptr, c_i32, c_i32, c_i64, c_ptr, c_ptr]),
     "mxm_observe_bases_labelled": (ctypes.c_int, [ctypes.POINTER(AlnColumns), c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i64,
                                                   c_ptr, c_ptr]),
+    "mxm_consensus": (ctypes.c_int, [c_ptr, c_i32, c_i64, c_i64, c_i64, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
+    "mxm_new_variants": (ctypes.c_int, [c_ptr, c_i64, c_i32, ctypes.POINTER(c_i32), c_i32, c_i64, c_ptr, c_ptr, c_ptr]),
+    "mxm_first_observed": (ctypes.c_int, [ctypes.POINTER(AlnColumns), c_ptr, c_ptr, c_i32, c_i32, c_i32, c_i64, c_ptr,
+                                          c_ptr, c_ptr]),
+    "mxm_extend_assign": (ctypes.c_int, [ctypes.POINTER(AlnColumns), c_ptr, c_ptr, c_i32, c_i32, ctypes.POINTER(c_i32),
+                                         c_i32, c_i32, c_i32, c_i32, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
     "mxm_set_compact_restarts": (ctypes.c_int, [c_i32]),
     "mxm_set_loop_graph": (ctypes.c_int, [c_i32]),
     "mxm_set_loop_fused": (ctypes.c_int, [c_i32, c_i32]),
@@ -167,7 +173,7 @@ SIGNATURES = {
 }
 
 # the MXM_VERSION of include/mixemt_hip.h these signatures were written for; load() refuses any other
-ABI_VERSION = 602
+ABI_VERSION = 603
 
 PROGRESS_FN = ctypes.CFUNCTYPE(None, ctypes.POINTER(EmState), c_i32, c_ptr)
 

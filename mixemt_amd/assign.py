@@ -14,6 +14,7 @@ reference's NumPy versions would need:
     assign_read_indexes        <- assemble.assign_read_indexes         assemble.py:284-334
                                   (with _find_best_n_for_read :267-281)
     assign_reads (ContribReads) <- assemble.assign_reads               assemble.py:233-264 (one label per alignment)
+                                  (consensus and extension over the labels: mixemt_amd/assemble.py)
 
 Matrices may be numpy arrays (uploaded) or ROCm tensors.
 """
@@ -365,6 +366,9 @@ class ContribReads(collections.abc.Mapping):
     (two contributors or more), -1 an alignment whose fragment is in no row (it is in no table, as in the reference,
     where its read id is in no row's list).
         labels        int32 device tensor [n_aln]; names: the label -> name list
+        joined        int32 device tensor [n_aln]: the extension round in which the alignment entered its list (0 =
+                      assign_reads; assemble.extend_assemblies writes it) -- the order of a list is (joined, index)
+        relabel(labels, joined=None)   take new labels (assemble's extension): counts and host copies are refreshed
         len(cr[name]) that contributor's alignment count (the "Reads" column of report_contributors)
         rows(name)    its alignment indexes (ascending: the file order the reference's lists keep), numpy int64
         as_dict(alns) the reference's dict: name -> [alns[i] for i in rows(name)] (indexes when alns is None)
@@ -373,17 +377,32 @@ class ContribReads(collections.abc.Mapping):
     report_contributors does that for every contributor before write_statistics iterates the keys.
     """
 
-    def __init__(self, cols, labels, names, keys, dcols=None):
+    def __init__(self, cols, labels, names, keys, dcols=None, frag=None):
         self.cols = cols                                     # alignments.AlignmentColumns the labels index
-        self.labels = labels
         self.names = list(names)
         self._keys = list(keys)
         self._dcols = dcols
+        self._frag = frag                                    # cols.frag on the device (made on demand)
+        self.rounds = 0                                      # extension rounds these labels have been through
+        self.relabel(labels, torch.zeros(labels.numel(), dtype=torch.int32, device=labels.device))
+
+    def relabel(self, labels, joined=None):
+        """Take new labels (and, when given, the rounds the alignments joined their lists in); the names and the keys
+        stay what they are."""
+        self.labels = labels
+        if joined is not None:
+            self.joined = joined
         n_labels = len(self.names)
         lab = labels[labels >= 0]
         self._counts = torch.bincount(lab.to(torch.int64), minlength=n_labels).cpu().numpy() if lab.numel() \
             else numpy.zeros(n_labels, dtype=numpy.int64)
         self._host = None
+
+    def device_frag(self):
+        """cols.frag (the alignments' fragment = query name) on the device, made once."""
+        if self._frag is None:
+            self._frag = torch.from_numpy(numpy.ascontiguousarray(self.cols.frag, dtype=numpy.int64)).to(self.labels.device)
+        return self._frag
 
     def device_columns(self):
         """The alignments uploaded for the labelled pileup (observe.DeviceColumns), made once."""
@@ -479,6 +498,7 @@ def assign_reads(cols, contribs, em_results, haps, reads, args, dcols=None):
         row_label = torch.zeros(len(reads), dtype=torch.int32, device=dev)
     ptr, group_frag = _row_groups(cols, reads)
     n_frag = max(len(cols.names), int(cols.frag.max()) + 1 if len(cols) else 0)
-    labels = alignment_labels(torch.from_numpy(cols.frag).to(dev), torch.from_numpy(ptr).to(dev),
-                              torch.from_numpy(group_frag).to(dev), row_label, n_frag)
-    return ContribReads(cols, labels, names, list(table), dcols)
+    frag_d = torch.from_numpy(cols.frag).to(dev)
+    labels = alignment_labels(frag_d, torch.from_numpy(ptr).to(dev), torch.from_numpy(group_frag).to(dev), row_label,
+                              n_frag)
+    return ContribReads(cols, labels, names, list(table), dcols, frag_d)

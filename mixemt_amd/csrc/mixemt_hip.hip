@@ -29,6 +29,8 @@
 //   fused_narrow_kernels.hpp  em_fused_narrow_kernel (the same for the refinement EM's few columns: the matrix in registers)
 //   aln_encode.hpp      HOST code: mxm_aln_encode, the batched alignment front end (process_reads + reduce_reads + row order)
 //   observe_kernels.hpp observe_bucket_kernel, observe_count_kernel (the pileup of the variant check: observe.py:56-86)
+//   assemble_kernels.hpp  consensus_kernel, new_variants_kernel, first_observed_kernel, extend_walk_kernel, extend_move_kernel
+//                       (consensus sequences and assembly extension over labelled pileups: assemble.py:431-585)
 // This file: the host side of the C ABI (shape checks, grid sizing, dispatch, the loop driver).
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -65,6 +67,7 @@
 #include "fused_narrow_kernels.hpp"
 #include "exchange.hpp"
 #include "observe_kernels.hpp"
+#include "assemble_kernels.hpp"
 
 
 // ------------------------------------------------------------------------------------------
@@ -2283,4 +2286,157 @@ extern "C" int mxm_observe_bases_labelled(const mxm_aln_columns *cols, const uin
                                           void *stream) {
     return observe_bases_impl<true>("mxm_observe_bases_labelled", cols, is_reverse, label, n_labels, min_mq, min_bq, L,
                                     counts, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// The assembly stage (assemble_kernels.hpp): consensus, new variants, the tie rule, extension.
+// ------------------------------------------------------------------------------------------
+extern "C" int mxm_consensus(const uint32_t *counts, int32_t n_labels, int64_t L, int64_t ref_len, int64_t min_cov,
+                             int32_t strict, uint8_t *cons, uint8_t *tied, uint32_t *n_tied, void *stream) {
+    if (n_labels < 0 || L < 0 || ref_len < 0) return fail(-1, "mxm_consensus: bad shape%s", "");
+    const int64_t n = (int64_t)n_labels * ref_len;
+    if (n == 0) return 0;
+    if (cons == nullptr || (counts == nullptr && L > 0)) return fail(-1, "mxm_consensus: counts and cons are required%s", "");
+    if ((reinterpret_cast<uintptr_t>(counts) & 15) != 0) return fail(-1, "mxm_consensus: counts must be 16-byte aligned%s", "");
+    hipLaunchKernelGGL(consensus_kernel, dim3(clamp_grid((n + ASM_THREADS - 1) / ASM_THREADS, num_cu() * 8)),
+                       dim3(ASM_THREADS), 0, (hipStream_t)stream, counts, n_labels, L, ref_len, min_cov, (int)(strict != 0),
+                       cons, tied, n_tied);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int asm_rows_from(const char *name, const int32_t *rows_host, int32_t n_use, int64_t n_rows, asm_rows *out) {
+    if (n_use < 0 || (n_use > 0 && rows_host == nullptr)) return fail(-1, "%s: bad participating rows", name);
+    if (n_use > ASM_MAX_USE)
+        return fail(-1, "%s: %lld participating contributors, at most %lld (an owner is an int8)", name, n_use, ASM_MAX_USE);
+    memset(out, 0, sizeof(*out));
+    for (int k = 0; k < n_use; ++k) {
+        if (rows_host[k] < 0 || rows_host[k] >= n_rows) return fail(-1, "%s: participating row %lld is no row", name, rows_host[k]);
+        out->row[k] = rows_host[k];
+    }
+    return 0;
+}
+
+extern "C" int mxm_new_variants(const uint8_t *cons, int64_t ld, int32_t n_rows, const int32_t *rows_host, int32_t n_use,
+                                int64_t ref_len, uint32_t *newvar, uint32_t *n_new, void *stream) {
+    if (ref_len < 0 || ld < ref_len || n_rows < 0) return fail(-1, "mxm_new_variants: bad shape%s", "");
+    asm_rows rows;
+    const int rc = asm_rows_from("mxm_new_variants", rows_host, n_use, n_rows, &rows);
+    if (rc) return rc;
+    if (ref_len == 0) return 0;
+    if (newvar == nullptr || n_new == nullptr || (cons == nullptr && n_use > 0))
+        return fail(-1, "mxm_new_variants: cons, newvar and n_new are required%s", "");
+    hipLaunchKernelGGL(new_variants_kernel, dim3(clamp_grid((ref_len + ASM_THREADS - 1) / ASM_THREADS, num_cu() * 8)),
+                       dim3(ASM_THREADS), 0, (hipStream_t)stream, cons, ld, rows, n_use, ref_len, newvar, n_new);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+static int asm_columns_ok(const char *name, const mxm_aln_columns *cols) {
+    if (cols == nullptr || cols->n_aln < 0) return fail(-1, "%s: bad arguments", name);
+    if (cols->n_aln > 0x7fffffffLL) return fail(-1, "%s: more than 2^31 - 1 alignments (%lld)", name, cols->n_aln);
+    if (cols->n_aln > 0 && (cols->ref_start == nullptr || cols->mapq == nullptr || cols->cig_ptr == nullptr ||
+                            cols->cigar == nullptr || cols->seq_ptr == nullptr || cols->seq == nullptr))
+        return fail(-1, "%s: ref_start, mapq, cig_ptr, cigar, seq_ptr and seq are required", name);
+    return 0;
+}
+
+static int asm_walk_error(const char *name, unsigned long long err_host, const char *kind3) {
+    if (err_host == OBS_ERR_NONE) return 0;
+    const long long i = (long long)(err_host >> 2);
+    switch ((int)(err_host & 3)) {
+        case 1: return fail(-4, "%s: the CIGAR of alignment %lld runs past its sequence", name, i);
+        case 2: return fail(-4, "%s: the CIGAR of alignment %lld holds an unknown operation", name, i);
+        default: snprintf(g_err, sizeof(g_err), "%s: alignment %lld %s", name, i, kind3); return -1;
+    }
+}
+
+extern "C" int mxm_first_observed(const mxm_aln_columns *cols, const int32_t *label, const int32_t *joined,
+                                  int32_t n_labels, int32_t min_mq, int32_t min_bq, int64_t ref_len, const uint8_t *tied,
+                                  uint8_t *cons, void *stream) {
+    const char *name = "mxm_first_observed";
+    const int rc = asm_columns_ok(name, cols);
+    if (rc) return rc;
+    if (n_labels < 0 || ref_len < 0) return fail(-1, "%s: bad shape", name);
+    const int64_t n = cols->n_aln, cells = (int64_t)n_labels * ref_len;
+    if (n == 0 || cells == 0) return 0;
+    if (label == nullptr || tied == nullptr || cons == nullptr) return fail(-1, "%s: label, tied and cons are required", name);
+    hipStream_t s = (hipStream_t)stream;
+    // scratch: first[cells][8] order keys (the size of the counts tables the consensus was called from), then the error word
+    void *scratch = nullptr;
+    HIP_TRY(hipMallocAsync(&scratch, ((size_t)cells * 8 + 1) * 8, s));
+    unsigned long long *first = static_cast<unsigned long long *>(scratch), *err = first + cells * 8;
+    unsigned long long err_host = OBS_ERR_NONE;
+    hipError_t e = hipMemsetAsync(scratch, 0xff, ((size_t)cells * 8 + 1) * 8, s);
+    if (e == hipSuccess) {
+        const int64_t blocks = (n + 63) / 64;
+        hipLaunchKernelGGL(first_observed_kernel, dim3(clamp_grid((blocks + 7) / 8, num_cu() * 4)), dim3(ASM_WALK_THREADS),
+                           0, s, cols->ref_start, cols->mapq, cols->cig_ptr, cols->cigar, cols->seq_ptr, cols->seq,
+                           cols->qual, cols->has_qual, label, joined, n_labels, n, min_mq, min_bq, ref_len, tied, first, err);
+        hipLaunchKernelGGL(first_resolve_kernel, dim3(clamp_grid((cells + ASM_THREADS - 1) / ASM_THREADS, num_cu() * 8)),
+                           dim3(ASM_THREADS), 0, s, tied, first, cells, cons);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&err_host, err, 8, hipMemcpyDeviceToHost, s);
+    }
+    const hipError_t ef = hipFreeAsync(scratch, s);
+    if (e == hipSuccess) e = ef;
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    HIP_TRY(e);
+    return asm_walk_error(name, err_host, "has a label >= n_labels");
+}
+
+extern "C" int mxm_extend_assign(const mxm_aln_columns *cols, int32_t *label, int32_t *joined, int32_t unassigned,
+                                 int32_t n_rows, const int32_t *rows_host, int32_t n_use, int32_t round, int32_t min_mq,
+                                 int32_t min_bq, const uint32_t *newvar, int64_t ref_len, int32_t *frag_state,
+                                 int32_t *moved_owner, uint32_t *n_moved, void *stream) {
+    const char *name = "mxm_extend_assign";
+    int rc = asm_columns_ok(name, cols);
+    if (rc) return rc;
+    asm_rows rows;
+    rc = asm_rows_from(name, rows_host, n_use, n_rows, &rows);
+    if (rc) return rc;
+    if (ref_len < 0 || cols->n_frag < 0 || round < 0) return fail(-1, "%s: bad shape", name);
+    const int64_t n = cols->n_aln, n_frag = cols->n_frag;
+    if (n == 0) return 0;
+    if (label == nullptr || joined == nullptr || cols->frag == nullptr || n_moved == nullptr ||
+        (n_frag > 0 && frag_state == nullptr) || (ref_len > 0 && newvar == nullptr))
+        return fail(-1, "%s: label, joined, frag, frag_state, newvar and n_moved are required", name);
+    hipStream_t s = (hipStream_t)stream;
+    unsigned long long *err = nullptr, err_host = OBS_ERR_NONE;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void **>(&err), 8, s));
+    hipError_t e = hipMemsetAsync(err, 0xff, 8, s);
+    if (e == hipSuccess && n_frag > 0) e = hipMemsetAsync(frag_state, 0xff, (size_t)n_frag * 4, s);   // ASM_FRAG_EMPTY
+    if (e == hipSuccess) {
+        const int64_t blocks = (n + 63) / 64;
+        const size_t lds = (size_t)ref_len * 4;
+        if (lds <= ASM_LDS_MAX_BYTES) {
+            // newvar in LDS: at most two workgroups per CU (each stages the whole table once and then walks many alignments)
+            const void *kernel = reinterpret_cast<const void *>(&extend_walk_kernel<true>);
+            if (lds > 65536) e = raise_dynamic_lds(kernel, lds, name);
+            if (e != hipSuccess) {
+                hipFreeAsync(err, s);
+                return -2;
+            }
+            const int per_cu = lds * 2 <= ASM_LDS_MAX_BYTES ? 2 : 1;
+            hipLaunchKernelGGL(extend_walk_kernel<true>, dim3(clamp_grid((blocks + 7) / 8, num_cu() * per_cu)),
+                               dim3(ASM_WALK_THREADS), lds, s, cols->ref_start, cols->mapq, cols->frag, cols->cig_ptr,
+                               cols->cigar, cols->seq_ptr, cols->seq, cols->qual, cols->has_qual, label, unassigned, n,
+                               n_frag, min_mq, min_bq, newvar, ref_len, frag_state, err);
+        } else {
+            hipLaunchKernelGGL(extend_walk_kernel<false>, dim3(clamp_grid((blocks + 7) / 8, num_cu() * 4)),
+                               dim3(ASM_WALK_THREADS), 0, s, cols->ref_start, cols->mapq, cols->frag, cols->cig_ptr,
+                               cols->cigar, cols->seq_ptr, cols->seq, cols->qual, cols->has_qual, label, unassigned, n,
+                               n_frag, min_mq, min_bq, newvar, ref_len, frag_state, err);
+        }
+        hipLaunchKernelGGL(extend_move_kernel, dim3(clamp_grid((n + ASM_THREADS - 1) / ASM_THREADS, num_cu() * 8)),
+                           dim3(ASM_THREADS), 0, s, cols->frag, n, n_frag, unassigned, rows, n_use, round, frag_state, label,
+                           joined, moved_owner, n_moved);
+        e = hipGetLastError();
+        if (e == hipSuccess) e = hipMemcpyAsync(&err_host, err, 8, hipMemcpyDeviceToHost, s);
+    }
+    const hipError_t ef = hipFreeAsync(err, s);
+    if (e == hipSuccess) e = ef;
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    HIP_TRY(e);
+    return asm_walk_error(name, err_host, "has a fragment index outside [0, n_frag)");
 }

@@ -11,6 +11,8 @@ The reference walks pysam's get_aligned_pairs(matches_only=False) one tuple at a
 library call (mxm_observe_bases, csrc/observe_kernels.hpp) counts every alignment's bases and gaps into the table.
 A character other than ACGTN is counted in the `other` bin of its strand: the reference keys it by the character itself;
 here it appears as 'X' (forward) / 'x' (reverse) in obs_at(pos) and obs_tab, and in write_base_obs' totals.
+A consensus (assemble.call_consensus) that such a character wins is 'X' too, and assemble.find_new_variants skips a
+position where a participating consensus is 'X': no read's real character could be looked up under it.
 """
 
 import collections

@@ -185,7 +185,7 @@ def _ragged(lengths):
 
 
 def synth_alignments(tables, refseq, n_frag, seed=1, contrib=DEFAULT_CONTRIB, props=DEFAULT_PROPS, mate_share=0.4,
-                     err=0.004, shuffle=True):
+                     err=0.004, shuffle=True, private=None):
     """
     -> alignments.AlignmentColumns of n_frag fragments (plus a mate for `mate_share` of them) shed by the three
     contributors' sequences (the reference sequence carrying the contributor's expected base at every variant site):
@@ -197,6 +197,9 @@ def synth_alignments(tables, refseq, n_frag, seed=1, contrib=DEFAULT_CONTRIB, pr
     that base sits on a variant site the fragment sees two different bases there.  Alignment order is shuffled.
     Strands (is_reverse): every mate reverse, half of the other alignments reverse -- drawn from a stream of their own,
     so that every other column is what it was before strands existed.
+    private: optional (contributor index, position, base) triples -- PRIVATE variants written into that contributor's
+    source sequence before it sheds reads (every read of the contributor over the position carries the base, no
+    haplogroup marker says so).  Editing the sources draws nothing from the generator: without it the output is unchanged.
     """
     from .alignments import AlignmentColumns
     rng = numpy.random.default_rng([int(seed), 0xA11])
@@ -208,6 +211,8 @@ def synth_alignments(tables, refseq, n_frag, seed=1, contrib=DEFAULT_CONTRIB, pr
         seq[sites] = tables.expected[:, col]
         srcs.append(seq)
     src = numpy.stack(srcs)                                              # [3][ref_len]
+    for k, pos, base in (private or ()):
+        src[int(k), int(pos)] = ord(base)
     who = rng.choice(len(props), size=n_frag, p=numpy.asarray(props, dtype=float))
     length = rng.integers(80, 151, size=n_frag)
     start = rng.integers(0, ref_len - 400, size=n_frag)

@@ -44,6 +44,13 @@ Fixtures (SURVEY.md section 8 c):
         assemble.assign_reads over the alignment objects, stats.report_contributors and stats.write_statistics in
         bin/mixemt's order (bin/mixemt:296-338), for three cases: default, every row unassigned (a huge min_fold),
         one contributor (a min_reads that leaves one candidate)
+    g18 mixemt's `-x` and `-b`: make_g18_alignments (synthetic fragments with PRIVATE variants planted in two contributors'
+        sources, hand-made reads on the uncovered tail of the reference for ties and gaps) through the reference's
+        pipeline as g17, then its own extend_assemblies / find_new_variants / call_consensus (both `strict`) /
+        report_contributors / write_statistics over the alignment objects: per round the counters and the new-variant
+        dict, the final key and the round of every alignment, the consensus strings, the verbose text and the files;
+        plus a case where nothing is assigned (no contributor keys) and one whose cons_cov calls nothing.
+        --cache DIR keeps the reference's matrix and EM result of g18 between runs of the generator.
 """
 
 import argparse
@@ -273,12 +280,77 @@ def _columns_sha(cols):
     return h.hexdigest()
 
 
+G18_SEED = 18          # synth_alignments seed of g18 (the section's asserts say what it was chosen for)
+G18_CONS_COV = 2
+G18_TAIL = 110         # the hand-made reads sit on the last G18_TAIL positions, which no synthetic read reaches
+
+
+def g18_private(refseq, tables):
+    """(contributor, position, base) of g18's planted variants: every 40 positions, off the Phylotree sites, for the
+    first two contributors (20 apart: a read of the third contributor shows the reference base at both, which belongs
+    to the OTHER contributor each time -- the fragments that see two owners), a base other than the reference's."""
+    sites = set(int(p) for p in tables.sites)
+    out = []
+    for k, first in ((0, 200), (1, 220)):
+        for pos in range(first, len(refseq) - 500, 40):
+            if pos not in sites and refseq[pos] in "ACGT":
+                out.append((k, pos, "ACGT"[("ACGT".index(refseq[pos]) + 1 + k) % 4]))
+    return out
+
+
+def make_g18_alignments(refseq, tables, n_frag=4000):
+    """synth_alignments with planted private variants + hand-made reads on the tail -> (AlignmentColumns, objects)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from _pileup_aln import PileupAln, from_columns
+    from mixemt_amd import synth
+    from mixemt_amd.alignments import AlignmentColumns
+    cols = synth.synth_alignments(tables, refseq, n_frag, seed=G18_SEED, private=g18_private(refseq, tables))
+    alns = from_columns(cols)
+    rng = numpy.random.default_rng(1818)
+    n = len(refseq)
+    t0 = n - G18_TAIL
+    M, D = 0, 2
+
+    def edited(start, length, edits):
+        seq = list(refseq[start:start + length])
+        for pos, base in edits:
+            seq[pos - start] = base
+        return "".join(seq)
+
+    def other(pos, step):
+        return "ACGT"[("ACGT".index(refseq[pos]) + step) % 4] if refseq[pos] in "ACGT" else "A"
+
+    sites = set(int(p) for p in tables.sites)
+    extra = []
+    # pairs of reads, one per strand, that disagree at five positions each (no Phylotree site: the pair shares its
+    # signature, so its row): 1 : 1 ties, decided by the file order
+    for k in range(6):
+        start = t0 + 2 * k
+        at = [p for p in range(start + 5 + k, start + 80, 3) if p not in sites][::5][:5]
+        extra.append(PileupAln("t_tie%d" % k, start, 60, edited(start, 80, [(p, other(p, 1 + k % 3)) for p in at]), [38] * 80,
+                               [(M, 80)], k % 2 == 0))
+        extra.append(PileupAln("t_tie%d_b" % k, start, 60, edited(start, 80, [(p, other(p, 1 + (k + 1) % 3)) for p in at]),
+                               [38] * 80, [(M, 80)], k % 2 == 1))
+    # two reads with the same deletion over positions nothing else covers (a gap called at coverage 2), and one with a
+    # deletion of its own under them (1 gap : 2 bases)
+    for k in range(3):
+        start = t0 + 1
+        d0, dlen = (n - 12, 3) if k < 2 else (n - 18, 2)
+        seq = refseq[start:d0] + refseq[d0 + dlen:d0 + dlen + 4]
+        extra.append(PileupAln("t_gap%d" % k, start, 60, seq, [38] * len(seq), [(M, d0 - start), (D, dlen), (M, 4)], k == 1))
+    order = rng.permutation(len(alns) + len(extra))
+    every = [(alns + extra)[k] for k in order]
+    cols = AlignmentColumns.from_alignments(every)
+    return cols, from_columns(cols)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--only", default="")
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"))
     ap.add_argument("--g10-rows", type=int, default=20000)
     ap.add_argument("--workers", type=int, default=6)
+    ap.add_argument("--cache", default="", help="g18: keep the reference's matrix and EM result in this directory")
     opts = ap.parse_args()
     only = set(x for x in opts.only.split(",") if x)
     os.makedirs(opts.out, exist_ok=True)
@@ -842,6 +914,220 @@ def main():
         out["toy_polymorphic"] = numpy.array(json.dumps(poly))
         save("g17_stats", seeds=numpy.array([G16_SEED, G16_EM_SEED, G17_REFINE_SEED]),
              columns_sha256=numpy.array(_columns_sha(cols)), **out)
+
+    if want("g18"):
+        for name in ("pysam", "Bio", "Bio.Seq", "Bio.SeqRecord", "Bio.SeqIO"):
+            sys.modules.setdefault(name, types.ModuleType(name))
+        sys.modules["Bio"].SeqIO = sys.modules["Bio.SeqIO"]
+        sys.modules["Bio.Seq"].Seq = object
+        sys.modules["Bio.SeqRecord"].SeqRecord = object
+        import collections
+        import json
+        import pickle
+        import tempfile
+        import mixemt.assemble
+        import mixemt.observe
+        import mixemt.stats
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from _pileup_aln import PileupBam
+        asm = ref.assemble
+        cols, alns = make_g18_alignments(refseq, tables)
+        cols_sha = _columns_sha(cols)
+        t0 = time.time()
+        obs = ref.observe.ObservedBases(alns, mapq=30, baseq=30)
+        read_obs = ref.preprocess.process_reads(alns, phy.get_variant_pos(), 30, 30)
+        read_sigs = ref.preprocess.reduce_reads(read_obs)
+        read_sigs.pop("", None)
+        rows = sorted(read_sigs)
+        reads = [read_sigs[r] for r in rows]
+        wts = numpy.array([len(r) for r in reads])
+        cache = os.path.join(opts.cache, "g18_%s.pkl" % cols_sha[:16]) if opts.cache else ""
+        if cache and os.path.exists(cache):
+            with open(cache, "rb") as fin:
+                mat, props, mix = pickle.load(fin)
+        else:
+            mat = ref.preprocess.build_em_matrix(refseq, phy, rows, haps, quiet)
+            props, mix, _, _ = ref_run_em(ref, mat, wts, G16_EM_SEED)
+            if cache:
+                with open(cache, "wb") as fout:
+                    pickle.dump((mat, props, mix), fout)
+        print("g18: pileup + matrix %d x %d + run_em in %.0f s" % (mat.shape[0], mat.shape[1], time.time() - t0), flush=True)
+        base = dict(min_reads=G16_MIN_READS, contributors=None, var_check=True, min_fold=2.0, min_var_reads=3,
+                    frac_var_reads=0.02, var_fraction=0.5, var_count=None, min_mq=30, min_bq=30, cons_cov=G18_CONS_COV)
+        cases = [("default", {}), ("nokeys", {"min_fold": 1e300}), ("nocall", {"cons_cov": 10 ** 6})]
+        index_of = {id(aln): i for i, aln in enumerate(alns)}
+        out = {}
+
+        def folded(alns_of):
+            """[ref_len][6] counts A C G T other gap of a list, N dropped (what consensus_base sees), and per position
+            the folded keys in first-observed order."""
+            tab = ref.observe.ObservedBases(alns_of, 30, 30) if alns_of else None
+            cnt, first = [], []
+            for pos in range(len(refseq)):
+                c = tab.obs_at(pos) if tab is not None else {}
+                keys = [k for k in c if k != "N" and c[k] > 0]
+                first.append(keys)
+                cnt.append([c.get(b, 0) for b in "ACGT"] + [sum(c[k] for k in keys if k not in "ACGT-"), c.get("-", 0)])
+            return numpy.array(cnt, dtype=numpy.int64), first
+
+        for label, kw in cases:
+            a = ns(**dict(base, **kw))
+            contribs = asm.get_contributors(phy, obs, haps, wts, (props, mix), a)
+            sub, sub_haps = ref.preprocess.reduce_em_matrix(mat, haps, contribs)
+            numpy.random.seed(G17_REFINE_SEED)
+            res = ref.em.run_em(sub, wts, a)
+            contribs = asm.update_contribs(contribs, res, sub_haps)
+            contrib_reads = asm.assign_reads(PileupBam(alns), contribs, res, sub_haps, reads, a)
+            names = [c[0] for c in contribs]
+            start_key = {id(aln): key for key in contrib_reads for aln in contrib_reads[key]}
+            strict_before = {key: asm.call_consensus(refseq, contrib_reads[key], a.cons_cov, a, strict=True)
+                             for key in list(contrib_reads)}
+            # the reference's own loop, with its two steps recorded as they run
+            rounds, dicts, moved_ids = [], [], []
+            real_find, real_assign = asm.find_new_variants, asm.assign_reads_from_new_vars
+
+            def rec_find(refseq_, cr, args_):
+                got = real_find(refseq_, cr, args_)
+                dicts.append(dict(got))
+                return got
+
+            def rec_assign(cr, new_variants, args_):
+                before = [id(x) for x in cr["unassigned"]]
+                cr = real_assign(cr, new_variants, args_)
+                after = set(id(x) for x in cr["unassigned"])
+                moved_ids.append([i for i in before if i not in after])
+                rounds.append((len(before) - len(after), len(before), len(new_variants)))
+                return cr
+
+            a.verbose = True
+            err, sys.stderr = sys.stderr, io.StringIO()
+            asm.find_new_variants, asm.assign_reads_from_new_vars = rec_find, rec_assign
+            try:
+                contrib_reads = asm.extend_assemblies(refseq, contrib_reads, a)
+                verbose_text = sys.stderr.getvalue()
+            finally:
+                sys.stderr = err
+                asm.find_new_variants, asm.assign_reads_from_new_vars = real_find, real_assign
+            a.verbose = False
+            keys_after_extend = list(contrib_reads)
+            strict_after = {key: asm.call_consensus(refseq, contrib_reads[key], a.cons_cov, a, strict=True)
+                            for key in keys_after_extend}
+            strict2_after = {key: asm.call_consensus(refseq, contrib_reads[key], 2, a, strict=True)
+                             for key in keys_after_extend}
+            loose_after = {key: asm.call_consensus(refseq, contrib_reads[key], 1, a, strict=False)
+                           for key in keys_after_extend}
+            report = io.StringIO()
+            ref.stats.report_contributors(report, contribs, contrib_reads)
+            with tempfile.TemporaryDirectory() as tmp:
+                a.stats_prefix = os.path.join(tmp, "run")
+                ref.stats.write_statistics(phy, obs, contribs, contrib_reads, a)
+                with open(a.stats_prefix + ".pos.tab") as fin:
+                    pos_tab = fin.read()
+                with open(a.stats_prefix + ".obs.tab") as fin:
+                    obs_tab = fin.read()
+            keys = sorted(contrib_reads)
+            key_of = {}
+            for k, key in enumerate(keys):
+                for aln in contrib_reads[key]:
+                    key_of[id(aln)] = k
+            aln_key = numpy.array([key_of.get(id(aln), -1) for aln in alns], dtype=numpy.int32)
+            aln_round = numpy.zeros(len(alns), dtype=numpy.int32)
+            for r, ids in enumerate(moved_ids):
+                aln_round[[index_of[i] for i in ids]] = r + 1
+            print("g18 %-8s: %d contributors, rounds (moved, unassigned, variants) %s" % (label, len(contribs), rounds), flush=True)
+
+            if label == "default":
+                assert len(contribs) >= 2
+                moving = [r for r in rounds if r[0] > 0]
+                assert len(moving) >= 2 and sum(r[0] for r in rounds) >= 50, rounds
+                assert rounds[-1][0] == 0
+                # a moved alignment below min_mq, or the mate of the one that showed the variant
+                moved = numpy.flatnonzero(aln_round > 0)
+                low = [i for i in moved if alns[i].mapping_quality < a.min_mq]
+                print("g18: %d alignments moved, %d of them below min_mq" % (len(moved), len(low)), flush=True)
+                assert low
+                # a fragment that saw two owners in round 1: re-walk the first round's unassigned list
+                seen = collections.defaultdict(set)
+                first_un = [x for x in alns if start_key.get(id(x)) == "unassigned"]
+                for aln in first_un:
+                    if aln.mapping_quality >= a.min_mq:
+                        for qpos, rpos in aln.get_aligned_pairs(matches_only=True):
+                            if aln.query_qualities is None or aln.query_qualities[qpos] >= a.min_bq:
+                                hit = dicts[0].get((rpos, aln.query_sequence[qpos].upper()))
+                                if hit is not None:
+                                    seen[aln.query_name].add(hit)
+                n_conflict = sum(1 for v in seen.values() if len(v) > 1)
+                print("g18: %d fragments with two owners in round 1" % n_conflict, flush=True)
+                assert n_conflict >= 1
+                # ties of the non-strict consensus, their winners, gaps
+                n_tie = n_not_first = n_rev_first = n_gap = n_gap_lift = 0
+                for key in keys_after_extend:
+                    lst = contrib_reads[key]
+                    if not lst:
+                        continue
+                    cnt, first = folded(lst)
+                    stranded = ref.observe.ObservedBases(lst, 30, 30)
+                    cons, cons2 = loose_after[key], strict2_after[key]
+                    for pos in range(len(refseq)):
+                        assert cons[pos] in "ACGTN-" and strict_after[key][pos] in "ACGTN-", (key, pos, cons[pos])
+                        c = cnt[pos]
+                        assert c[4] == 0, (key, pos)               # no character outside ACGTN- is observed at all
+                        if cons[pos] == "-":
+                            n_gap += 1
+                        if cons2[pos] == "-" and c[:5].sum() < 2:
+                            n_gap_lift += 1
+                        top = c.max()
+                        if top > 0 and (c == top).sum() > 1:
+                            n_tie += 1
+                            tied = [b for b, v in zip("ACGTX-", c) if v == top]
+                            assert cons[pos] in tied
+                            if cons[pos] != sorted(tied)[0]:
+                                n_not_first += 1
+                            raw = list(stranded.obs_tab[pos])      # stranded keys in the order they were first observed
+                            lead = [k for k in raw if k.upper() in tied or (k == "+" and "-" in tied)]
+                            if lead and (lead[0].islower() or lead[0] == "+"):
+                                n_rev_first += 1
+                print("g18: %d tied positions, %d won by a base that is not the alphabetically first, %d first seen on the "
+                      "reverse strand; %d gap calls, %d where gaps make the coverage" % (n_tie, n_not_first, n_rev_first, n_gap,
+                                                                                      n_gap_lift), flush=True)
+                assert n_tie >= 5 and n_not_first >= 1 and n_rev_first >= 1 and n_gap >= 1 and n_gap_lift >= 1
+            elif label == "nokeys":
+                assert len(contribs) >= 2 and dicts == [{}] and rounds[0][0] == 0 and len(rounds) == 1
+            else:
+                assert all(len(d) == 0 for d in dicts) and len(rounds) == 1 and rounds[0][0] == 0
+
+            out[label + "_contribs"] = numpy.array("\n".join("%s\t%s\t%r" % (c[0], c[1], float(c[2])) for c in contribs))
+            out[label + "_args"] = numpy.array(json.dumps(dict(kw, cons_cov=a.cons_cov)))
+            out[label + "_rounds"] = numpy.array(rounds, dtype=numpy.int64).reshape(-1, 3)
+            for r, d in enumerate(dicts):
+                items = sorted(d.items())
+                out["%s_nv%d_pos" % (label, r)] = numpy.array([k[0] for k, _ in items], dtype=numpy.int64)
+                out["%s_nv%d_base" % (label, r)] = numpy.array("".join(k[1] for k, _ in items))
+                out["%s_nv%d_own" % (label, r)] = numpy.array([names.index(v) for _, v in items], dtype=numpy.int32)
+            out[label + "_start_keys"] = numpy.array("\n".join(strict_before))
+            out[label + "_start_key"] = numpy.array([list(strict_before).index(start_key[id(x)]) if id(x) in start_key else -1
+                                                     for x in alns], dtype=numpy.int32)
+            out[label + "_extend_keys"] = numpy.array("\n".join(keys_after_extend))
+            out[label + "_keys"] = numpy.array("\n".join(keys))
+            out[label + "_aln_key"] = aln_key
+            out[label + "_aln_round"] = aln_round
+            out[label + "_strict_before"] = numpy.array(json.dumps(strict_before))
+            out[label + "_strict_after"] = numpy.array(json.dumps(strict_after))
+            out[label + "_strict2_after"] = numpy.array(json.dumps(strict2_after))
+            out[label + "_loose_after"] = numpy.array(json.dumps(loose_after))
+            out[label + "_verbose"] = numpy.array(verbose_text)
+            out[label + "_report"] = numpy.array(report.getvalue())
+            if label == "default":
+                out[label + "_pos_tab"] = numpy.array(pos_tab)
+                out[label + "_obs_tab"] = numpy.array(obs_tab)
+        trip = [(pos, key, cnt) for pos in sorted(obs.obs_tab) for key, cnt in sorted(obs.obs_tab[pos].items())]
+        save("g18_assemble", seeds=numpy.array([G18_SEED, G16_EM_SEED, G17_REFINE_SEED]),
+             columns_sha256=numpy.array(cols_sha), n_aln=numpy.array(len(cols)),
+             trip_pos=numpy.array([t[0] for t in trip], dtype=numpy.int64),
+             trip_key=numpy.array("".join(t[1] for t in trip)),
+             trip_count=numpy.array([t[2] for t in trip], dtype=numpy.int64),
+             signatures_sha256=numpy.array(hashlib.sha256("\n".join(rows).encode()).hexdigest()),
+             props=props, **out)
 
     if want("g7"):
         cols = list(range(0, 5400, 54))

@@ -8,6 +8,7 @@ synthetic reads, device-resident end to end:
 
     python tools/run_pipeline.py [--reads N] [--seed S] [--multi M] [--dense [--storage f64|f32|coded|auto]] [--alignments]
                                  [--pairs | --read-len L] [--var-check [-R N] [-F F] [-f F] [-n N]] [--stats PREFIX]
+                                 [--extend [--cons-cov N]] [--cons PREFIX]
 
 --alignments (round 5): start one step earlier, from ALIGNMENTS -- N synthetic fragments (synth-aln-v1: mates, indels,
 clips, low qualities, duplicates) as columns -> the library's batched front end (alignments.encode_alignments =
@@ -22,6 +23,12 @@ default in bin/mixemt) over a pileup of the same columns (observe.observe_bases)
 contributors (assign.assign_reads: one label per alignment on the device), the contributor table is the reference's
 report_contributors (its Reads column counts alignments), and stats.write_statistics writes PREFIX.pos.tab and
 PREFIX.obs.tab (every contributor's pileup from one labelled call).  Without it the output is what it was.
+
+--extend / --cons PREFIX (with --alignments, opt-in): bin/mixemt's -x and -b PREFIX in its order (bin/mixemt:329-340):
+after the alignments went to their contributors, assemble.extend_assemblies moves unassigned fragments that show ONE
+contributor's new variants (--cons-cov N: the coverage of a consensus call, bin/mixemt's -c, default 2; only with more
+than one contributor), the contributor table is printed with the post-extension counts, then --stats' tables, then
+PREFIX.fa with every contributor's majority consensus (assemble.write_consensus_seqs).
 
 Default (round 3): the build leaves the matrix as row-dictionary records -- no dense matrix, no posterior matrix; the
 contributors, the vote table and the reduced matrix for the refinement come from the records.  --dense takes the
@@ -66,6 +73,12 @@ def main():
     ap.add_argument("-n", "--var-count", dest="var_count", type=int, default=None)
     ap.add_argument("--stats", dest="stats_prefix", default=None, metavar="PREFIX",
                     help="with --alignments: write mixemt's -t tables PREFIX.pos.tab and PREFIX.obs.tab (stats.py:138-171)")
+    ap.add_argument("--extend", action="store_true",
+                    help="with --alignments: mixemt's -x, the assembly extension (assemble.py:549-585), before the table is printed")
+    ap.add_argument("--cons-cov", dest="cons_cov", type=int, default=2, metavar="N",
+                    help="with --extend: coverage required to call a contributor's consensus base (mixemt's -c)")
+    ap.add_argument("--cons", dest="cons_prefix", default=None, metavar="PREFIX",
+                    help="with --alignments: write mixemt's -b file PREFIX.fa (assemble.py:396-428)")
     ap.add_argument("--threads", type=int, default=0, help="with --alignments: host threads of the encoder (0 = its default)")
     ap.add_argument("--storage", default="auto", choices=["f64", "f32", "coded", "auto"],
                     help="with --dense: form of the matrix the EM loop streams (EmPlan): coded = lossless row dictionaries, "
@@ -76,6 +89,8 @@ def main():
         ap.error("--var-check needs --alignments (the pileup is made from the alignments)")
     if opts.stats_prefix and not opts.alignments:
         ap.error("--stats needs --alignments (the tables are pileups of the alignments)")
+    if (opts.extend or opts.cons_prefix) and not opts.alignments:
+        ap.error("--extend and --cons need --alignments (they work on the alignments of each contributor)")
     args = argparse.Namespace(init_alpha=1.0, tolerance=1e-4, max_iter=10000, n_multi=opts.multi,
                               verbose=True, min_reads=10, min_fold=2.0, storage=opts.storage)
     numpy.random.seed(opts.seed)                       # bin/mixemt:507-508
@@ -249,14 +264,28 @@ def main():
                      % (opts.reads, (time.perf_counter() - t0) * 1e3))
 
     sys.stderr.write("tables -> read assignment, all stages: %.1f ms\n" % ((time.perf_counter() - t_all) * 1e3))
-    if opts.stats_prefix:
-        from mixemt_amd import stats
+    if opts.stats_prefix or opts.extend or opts.cons_prefix:
+        from mixemt_amd import assemble, stats
         t0 = time.perf_counter()
-        contrib_reads = assign.assign_reads(cols, contribs, results, sub_haps, reads, args, dcols)
+        contrib_reads = assign.assign_reads(cols, contribs, results, sub_haps, reads, args, dcols if opts.stats_prefix else None)
         torch.cuda.synchronize()
         t1 = time.perf_counter()
+        asm = argparse.Namespace(min_mq=30, min_bq=30, cons_cov=opts.cons_cov, cons_prefix=opts.cons_prefix, verbose=True)
+        if opts.extend and len(contribs) > 1:
+            te = time.perf_counter()
+            contrib_reads = assemble.extend_assemblies(refseq, contrib_reads, asm)
+            torch.cuda.synchronize()
+            sys.stderr.write("assembly extension (%d rounds): %.1f ms\n" % (contrib_reads.rounds, (time.perf_counter() - te) * 1e3))
         stats.report_contributors(sys.stdout, contribs, contrib_reads)
         sys.stdout.flush()
+        if opts.cons_prefix:
+            tc = time.perf_counter()
+            assemble.write_consensus_seqs(refseq, contribs, contrib_reads, asm)
+            t_cons = (time.perf_counter() - tc) * 1e3
+        if not opts.stats_prefix:
+            if opts.cons_prefix:
+                sys.stderr.write("-b output: %.1f ms: %s.fa\n" % (t_cons, opts.cons_prefix))
+            return 0
         st = argparse.Namespace(stats_prefix=opts.stats_prefix, min_mq=30, min_bq=30, min_var_reads=opts.min_var_reads,
                                 frac_var_reads=opts.frac_var_reads)
         t2 = time.perf_counter()
@@ -266,6 +295,8 @@ def main():
                          "tables + both files) %.1f ms: %s.pos.tab, %s.obs.tab\n"
                          % ((t1 - t0) * 1e3, len(contrib_reads.names), (t3 - t2) * 1e3, opts.stats_prefix,
                             opts.stats_prefix))
+        if opts.cons_prefix:
+            sys.stderr.write("-b output: %.1f ms: %s.fa\n" % (t_cons, opts.cons_prefix))
         return 0
     print("hap#   Haplogroup      Contribution   Reads")
     print("-------------------------------------------")
