@@ -8,7 +8,8 @@
 //   first_resolve_kernel   the contributor's alignment list (order key (joined, index)), only at tied positions
 //   extend_walk_kernel     assign_reads_from_new_vars (assemble.py:504-546): the owners an unassigned fragment's bases
 //   extend_move_kernel     show, folded into one state per fragment; then the move of the fragments with ONE owner
-// The alignment walk (CIGAR, query offsets, quality rule) is observe_count_kernel's (observe_kernels.hpp).
+// The alignment walk (CIGAR, query offsets, quality rule), the wave-per-alignment loop and the error word are
+// aln_walk.hpp's.
 #ifndef MIXEMT_ASSEMBLE_KERNELS_HPP
 #define MIXEMT_ASSEMBLE_KERNELS_HPP
 
@@ -90,8 +91,8 @@ __global__ __launch_bounds__(ASM_THREADS) void consensus_kernel(const uint32_t *
 }
 
 __device__ __forceinline__ int asm_acgt(uint8_t b) {
-    if (b >= 'a' && b <= 'z') b = (uint8_t)(b - 32);
-    return b == 'A' ? 0 : b == 'C' ? 1 : b == 'G' ? 2 : b == 'T' ? 3 : -1;
+    const int bin = obs_base_bin(b);
+    return bin < 4 ? bin : -1;
 }
 
 // A thread per position: newvar[pos] = four int8 owners (A, C, G, T; -1 none), owner k = the k-th participating row.
@@ -133,75 +134,36 @@ __global__ __launch_bounds__(ASM_THREADS) void new_variants_kernel(const uint8_t
     if ((threadIdx.x & 63) == 0 && mine) atomicAdd(n_new, mine);
 }
 
-// error word as observe_kernels.hpp: (alignment index << 2) | kind, kind 1 = CIGAR past the sequence, 2 = unknown
-// operation, 3 = a fragment index outside [0, n_frag) (extend) / a label >= n_labels (first observed)
-__device__ __forceinline__ void asm_error(unsigned long long *err, int64_t i, unsigned kind) {
-    atomicMin(err, ((unsigned long long)i << 2) | kind);
-}
-
 // A wave per alignment of a labelled list (label in [0, n_labels), mapq >= min_mq, placed): every observation the
 // pileup counts at a position whose `tied` byte is set offers its order key -- (joined << 32) | index, the place of the
 // alignment in its contributor's list -- to first[(label * ref_len + pos) * 8 + folded bin] by atomicMin.  Positions
-// that are not tied cost one byte read and no atomic.
+// that are not tied cost one byte read and no atomic.  Error kind 3: a label >= n_labels.
 __global__ __launch_bounds__(ASM_WALK_THREADS) void first_observed_kernel(
-    const int64_t *__restrict__ ref_start, const int32_t *__restrict__ mapq, const int64_t *__restrict__ cig_ptr,
-    const uint32_t *__restrict__ cigar, const int64_t *__restrict__ seq_ptr, const uint8_t *__restrict__ seq,
-    const uint8_t *__restrict__ qual, const uint8_t *__restrict__ has_qual, const int32_t *__restrict__ label,
-    const int32_t *__restrict__ joined, int32_t n_labels, int64_t n_aln, int32_t min_mq, int32_t min_bq, int64_t ref_len,
-    const uint8_t *__restrict__ tied, unsigned long long *__restrict__ first, unsigned long long *err) {
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t n_wave = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t i0 = wave * 64; i0 < n_aln; i0 += n_wave * 64) {
-        const int64_t mine = i0 + lane;
-        bool use = false;
-        if (mine < n_aln) {
-            const int32_t lab = label[mine];
-            if (lab >= n_labels) asm_error(err, mine, 3);
-            use = lab >= 0 && lab < n_labels && mapq[mine] >= min_mq && ref_start[mine] >= 0;
-        }
-        unsigned long long todo = __ballot(use);
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const int64_t i = i0 + src;
+    aln_view aln, const int32_t *__restrict__ label, const int32_t *__restrict__ joined, int32_t n_labels,
+    int64_t ref_len, const uint8_t *__restrict__ tied, unsigned long long *__restrict__ first, unsigned long long *err) {
+    aln_for_each(
+        aln.n_aln,
+        [&](int64_t i) {
+            const int32_t lab = label[i];
+            if (lab >= n_labels) aln_error(err, i, 3);
+            return lab >= 0 && lab < n_labels && obs_counts(aln.ref_start, aln.mapq, aln.min_mq, i);
+        },
+        [&](int64_t i, int lane) {
             const int64_t lab = label[i];
             const unsigned long long key = ((unsigned long long)(uint32_t)(joined != nullptr ? joined[i] : 0) << 32) |
                                            (unsigned long long)i;
-            const int64_t s0 = seq_ptr[i], slen = seq_ptr[i + 1] - s0;
-            const bool has_q = qual != nullptr && (has_qual == nullptr || has_qual[i] != 0);
-            int64_t r = ref_start[i], q = 0;
-            for (int64_t k = cig_ptr[i]; k < cig_ptr[i + 1]; ++k) {
-                const uint32_t op = cigar[k] & 15u;
-                const int64_t len = (int64_t)(cigar[k] >> 4);
-                const bool match = op == 0 || op == 7 || op == 8, gap = op == 2 || op == 3;
-                if (op > 8) {
-                    if (lane == 0) asm_error(err, i, 2);
-                    break;
+            aln_walk(aln, i, lane, err, [&](bool match, int64_t r, int64_t qp, int64_t len, bool has_q) -> unsigned {
+                const int64_t stop = min(len, ref_len - r);              // positions past ref_len have no consensus
+                for (int64_t j = lane; j < stop; j += 64) {
+                    const int64_t cell = lab * ref_len + r + j;
+                    const uint8_t m = tied[cell];
+                    if (!m) continue;
+                    const int bin = match ? aln_base_bin(aln, has_q, qp + j) : 6;
+                    if ((m >> bin) & 1) atomicMin(&first[cell * 8 + bin], key);
                 }
-                if (match && q + len > slen) {
-                    if (lane == 0) asm_error(err, i, 1);
-                    break;
-                }
-                if (match || gap) {
-                    const int64_t stop = min(len, ref_len - r);              // positions past ref_len have no consensus
-                    for (int64_t j = lane; j < stop; j += 64) {
-                        const int64_t cell = lab * ref_len + r + j;
-                        const uint8_t m = tied[cell];
-                        if (!m) continue;
-                        int bin = 6;
-                        if (match) {
-                            const int64_t qp = s0 + q + j;
-                            bin = (has_q && (int32_t)qual[qp] < min_bq) ? 4 : obs_base_bin(seq[qp]);
-                        }
-                        if ((m >> bin) & 1) atomicMin(&first[cell * 8 + bin], key);
-                    }
-                }
-                if (match || op == 1 || op == 4) q += len;
-                if (match || gap) r += len;
-            }
-        }
-    }
+                return 0;
+            });
+        });
 }
 
 // A thread per (table, position): at a tied position the bin of the mask with the smallest key is the consensus.
@@ -233,65 +195,38 @@ __device__ __forceinline__ int asm_merge(int a, int b) {
 // query, D / N the reference: get_aligned_pairs(matches_only=True)); a base counts when the alignment has no qualities
 // or its quality is >= min_bq; its upper-cased character is looked up in newvar (staged in LDS when IN_LDS).  The wave
 // merges its lanes' owners and folds ONE state into frag_state[fragment]: the final state does not depend on the order.
+// Error kind 3: a fragment index outside [0, n_frag) (the alignment is skipped).
 template <bool IN_LDS>
 __global__ __launch_bounds__(ASM_WALK_THREADS) void extend_walk_kernel(
-    const int64_t *__restrict__ ref_start, const int32_t *__restrict__ mapq, const int64_t *__restrict__ frag,
-    const int64_t *__restrict__ cig_ptr, const uint32_t *__restrict__ cigar, const int64_t *__restrict__ seq_ptr,
-    const uint8_t *__restrict__ seq, const uint8_t *__restrict__ qual, const uint8_t *__restrict__ has_qual,
-    const int32_t *__restrict__ label, int32_t unassigned, int64_t n_aln, int64_t n_frag, int32_t min_mq, int32_t min_bq,
+    aln_view aln, const int64_t *__restrict__ frag, const int32_t *__restrict__ label, int32_t unassigned, int64_t n_frag,
     const uint32_t *__restrict__ newvar, int64_t ref_len, int32_t *__restrict__ frag_state, unsigned long long *err) {
     extern __shared__ uint32_t nv_lds[];
     if (IN_LDS) {
         for (int64_t k = threadIdx.x; k < ref_len; k += blockDim.x) nv_lds[k] = newvar[k];
         __syncthreads();
     }
-    const int lane = threadIdx.x & 63;
-    const int64_t wave = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-    const int64_t n_wave = ((int64_t)gridDim.x * blockDim.x) >> 6;
-    for (int64_t i0 = wave * 64; i0 < n_aln; i0 += n_wave * 64) {
-        const int64_t mine = i0 + lane;
-        const bool use = mine < n_aln && label[mine] == unassigned && mapq[mine] >= min_mq && ref_start[mine] >= 0;
-        unsigned long long todo = __ballot(use);
-        while (todo) {
-            const int src = __ffsll((long long)todo) - 1;
-            todo &= todo - 1;
-            const int64_t i = i0 + src;
+    aln_for_each(
+        aln.n_aln,
+        [&](int64_t i) { return label[i] == unassigned && obs_counts(aln.ref_start, aln.mapq, aln.min_mq, i); },
+        [&](int64_t i, int lane) {
             const int64_t f = frag[i];
             if (f < 0 || f >= n_frag) {
-                if (lane == 0) asm_error(err, i, 3);
-                continue;
+                if (lane == 0) aln_error(err, i, 3);
+                return;
             }
-            const int64_t s0 = seq_ptr[i], slen = seq_ptr[i + 1] - s0;
-            const bool has_q = qual != nullptr && (has_qual == nullptr || has_qual[i] != 0);
-            int64_t r = ref_start[i], q = 0;
             int state = ASM_FRAG_EMPTY;
-            for (int64_t k = cig_ptr[i]; k < cig_ptr[i + 1]; ++k) {
-                const uint32_t op = cigar[k] & 15u;
-                const int64_t len = (int64_t)(cigar[k] >> 4);
-                const bool match = op == 0 || op == 7 || op == 8, gap = op == 2 || op == 3;
-                if (op > 8) {
-                    if (lane == 0) asm_error(err, i, 2);
-                    break;
+            aln_walk(aln, i, lane, err, [&](bool match, int64_t r, int64_t qp, int64_t len, bool has_q) -> unsigned {
+                if (!match) return 0;
+                const int64_t stop = min(len, ref_len - r);              // newvar ends at ref_len
+                for (int64_t j = lane; j < stop; j += 64) {
+                    const int b = aln_base_bin(aln, has_q, qp + j);
+                    if (b > 3) continue;                                 // a low quality, N or no base at all
+                    const uint32_t word = IN_LDS ? nv_lds[r + j] : newvar[r + j];
+                    const int owner = (int)(int8_t)(uint8_t)(word >> (8 * b));
+                    if (owner >= 0) state = asm_merge(state, owner);
                 }
-                if (match && q + len > slen) {
-                    if (lane == 0) asm_error(err, i, 1);
-                    break;
-                }
-                if (match) {
-                    const int64_t stop = min(len, ref_len - r);              // newvar ends at ref_len
-                    for (int64_t j = lane; j < stop; j += 64) {
-                        const int64_t qp = s0 + q + j;
-                        if (has_q && (int32_t)qual[qp] < min_bq) continue;
-                        const int b = asm_acgt(seq[qp]);
-                        if (b < 0) continue;
-                        const uint32_t word = IN_LDS ? nv_lds[r + j] : newvar[r + j];
-                        const int owner = (int)(int8_t)(uint8_t)(word >> (8 * b));
-                        if (owner >= 0) state = asm_merge(state, owner);
-                    }
-                }
-                if (match || op == 1 || op == 4) q += len;
-                if (match || gap) r += len;
-            }
+                return 0;
+            });
 #pragma unroll
             for (int off = 32; off > 0; off >>= 1) state = asm_merge(state, __shfl_xor(state, off, 64));
             if (lane == 0 && state != ASM_FRAG_EMPTY) {
@@ -303,8 +238,7 @@ __global__ __launch_bounds__(ASM_WALK_THREADS) void extend_walk_kernel(
                     if (old != ASM_FRAG_EMPTY && old != state) atomicExch(cell, ASM_FRAG_CONFLICT);
                 }
             }
-        }
-    }
+        });
 }
 
 // A thread per alignment: an unassigned alignment (whatever its mapq) whose fragment has ONE owner takes the owner's

@@ -66,6 +66,7 @@
 #include "fused_coded_kernels.hpp"
 #include "fused_narrow_kernels.hpp"
 #include "exchange.hpp"
+#include "aln_walk.hpp"
 #include "observe_kernels.hpp"
 #include "assemble_kernels.hpp"
 
@@ -2211,8 +2212,50 @@ extern "C" int mxm_fold_logaddexp(double *acc, int64_t lda, const double *const 
     return 0;
 }
 
-// The pileup (observe_kernels.hpp).  Blocking: the scratch is stream-ordered memory of the call's own, and the error word
-// is read back before returning.  LABELLED: n_labels tables counts[n_labels][L][16], alignment i into table label[i]
+// ------------------------------------------------------------------------------------------
+// Host side of the three entries that walk alignments on the device (aln_walk.hpp): the pileup, the tie rule, the
+// extension.  Each is blocking: its scratch is stream-ordered memory of the call's own, and the error word is read
+// back before returning.
+// ------------------------------------------------------------------------------------------
+static int aln_columns_ok(const char *name, const mxm_aln_columns *cols) {
+    if (cols == nullptr || cols->n_aln < 0) return fail(-1, "%s: bad arguments", name);
+    if (cols->n_aln > 0x7fffffffLL) return fail(-1, "%s: more than 2^31 - 1 alignments (%lld)", name, cols->n_aln);
+    if (cols->n_aln > 0 && (cols->ref_start == nullptr || cols->mapq == nullptr || cols->cig_ptr == nullptr ||
+                            cols->cigar == nullptr || cols->seq_ptr == nullptr || cols->seq == nullptr))
+        return fail(-1, "%s: ref_start, mapq, cig_ptr, cigar, seq_ptr and seq are required", name);
+    return 0;
+}
+
+// One pass with an error word: `enqueue(scratch, err)` puts the call's work on the stream (scratch: `bytes` of its own,
+// 8-byte aligned; err: the word, ALN_ERR_NONE) and returns the first HIP error it met; the word is copied to *err_host,
+// the memory released and the stream synchronised.  The first HIP error wins; after one nothing is waited for.
+template <typename F>
+static hipError_t aln_pass(hipStream_t s, size_t bytes, unsigned long long *err_host, F enqueue) {
+    unsigned long long *err = nullptr;
+    *err_host = ALN_ERR_NONE;
+    hipError_t e = hipMallocAsync(reinterpret_cast<void **>(&err), 8 + bytes, s);
+    if (e != hipSuccess) return e;
+    e = hipMemsetAsync(err, 0xff, 8, s);
+    if (e == hipSuccess) e = enqueue(static_cast<void *>(err + 1), err);
+    if (e == hipSuccess) e = hipMemcpyAsync(err_host, err, 8, hipMemcpyDeviceToHost, s);
+    const hipError_t ef = hipFreeAsync(err, s);
+    if (e == hipSuccess) e = ef;
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    return e;
+}
+
+// The error word as a return code and message; kind3 / kind0: the caller's text after "alignment N " for its own kinds.
+static int aln_walk_error(const char *name, unsigned long long err_host, const char *kind3, const char *kind0 = nullptr) {
+    if (err_host == ALN_ERR_NONE) return 0;
+    const long long i = (long long)(err_host >> 2);
+    const int kind = (int)(err_host & 3);
+    if (kind == 1) return fail(-4, "%s: the CIGAR of alignment %lld runs past its sequence", name, i);
+    if (kind == 2) return fail(-4, "%s: the CIGAR of alignment %lld holds an unknown operation", name, i);
+    snprintf(g_err, sizeof(g_err), "%s: alignment %lld %s", name, i, kind == 0 && kind0 != nullptr ? kind0 : kind3);
+    return -1;
+}
+
+// The pileup (observe_kernels.hpp).  LABELLED: n_labels tables counts[n_labels][L][16], alignment i into table label[i]
 // (negative: not counted); otherwise one table and `label` / n_labels are not read.
 template <bool LABELLED>
 static int observe_bases_impl(const char *name, const mxm_aln_columns *cols, const uint8_t *is_reverse,
@@ -2220,28 +2263,24 @@ static int observe_bases_impl(const char *name, const mxm_aln_columns *cols, con
                               uint32_t *counts, void *stream) {
     if (cols == nullptr || cols->n_aln < 0 || L < 0 || (L > 0 && n_labels > 0 && counts == nullptr))
         return fail(-1, "%s: bad arguments", name);
-    const int64_t n = cols->n_aln;
     if (LABELLED && n_labels < 0) return fail(-1, "%s: n_labels < 0 (%lld)", name, n_labels);
+    const int rc = aln_columns_ok(name, cols);
+    if (rc) return rc;
+    const int64_t n = cols->n_aln;
     if (n == 0) return 0;
-    if (n > 0x7fffffffLL) return fail(-1, "%s: more than 2^31 - 1 alignments (%lld)", name, n);
-    if (cols->ref_start == nullptr || cols->mapq == nullptr || cols->cig_ptr == nullptr || cols->cigar == nullptr ||
-        cols->seq_ptr == nullptr || cols->seq == nullptr)
-        return fail(-1, "%s: ref_start, mapq, cig_ptr, cigar, seq_ptr and seq are required", name);
     if (LABELLED && label == nullptr) return fail(-1, "%s: label is required", name);
     hipStream_t s = (hipStream_t)stream;
     const int64_t nb = (L + OBS_BUCKET - 1) / OBS_BUCKET;   // windows of one table
     const int64_t nbk = LABELLED ? nb * (int64_t)n_labels : nb;
-    // scratch: cnt[nbk], cursor[nbk], off[nbk + 1], chunk_off[nbk + 1], err, then perm[n] (int32)
-    const size_t words = (size_t)(4 * nbk + 3);
-    void *scratch = nullptr;
-    HIP_TRY(hipMallocAsync(&scratch, words * 8 + (size_t)n * 4, s));
-    unsigned long long *cnt = static_cast<unsigned long long *>(scratch), *cursor = cnt + nbk, *off = cursor + nbk,
-                       *chunk_off = off + nbk + 1, *err = chunk_off + nbk + 1;
-    int32_t *perm = reinterpret_cast<int32_t *>(err + 1);
-    unsigned long long err_host = OBS_ERR_NONE;
-    hipError_t e = hipMemsetAsync(cnt, 0, (size_t)nbk * 8, s);
-    if (e == hipSuccess) e = hipMemsetAsync(err, 0xff, 8, s);
-    if (e == hipSuccess) {
+    // scratch: cnt[nbk], cursor[nbk], off[nbk + 1], chunk_off[nbk + 1], then perm[n] (int32)
+    unsigned long long err_host;
+    const size_t bytes = (size_t)(4 * nbk + 2) * 8 + (size_t)n * 4;
+    HIP_TRY(aln_pass(s, bytes, &err_host, [&](void *scratch, unsigned long long *err) {
+        unsigned long long *cnt = static_cast<unsigned long long *>(scratch), *cursor = cnt + nbk, *off = cursor + nbk,
+                           *chunk_off = off + nbk + 1;
+        int32_t *perm = reinterpret_cast<int32_t *>(chunk_off + nbk + 1);
+        const hipError_t e = hipMemsetAsync(cnt, 0, (size_t)nbk * 8, s);
+        if (e != hipSuccess) return e;
         const unsigned grid_b = (unsigned)((n + OBS_BKT_PER_WG - 1) / OBS_BKT_PER_WG);
         hipLaunchKernelGGL((observe_bucket_kernel<LABELLED, 0>), dim3(grid_b), dim3(OBS_BKT_THREADS), 0, s,
                            cols->ref_start, cols->mapq, label, n_labels, n, min_mq, L, nb, nbk, cnt, perm, err);
@@ -2250,29 +2289,15 @@ static int observe_bases_impl(const char *name, const mxm_aln_columns *cols, con
                            cols->ref_start, cols->mapq, label, n_labels, n, min_mq, L, nb, nbk, cursor, perm, err);
         // at most one partial chunk per bucket beyond the full ones
         const int64_t grid_c = (n + OBS_CHUNK - 1) / OBS_CHUNK + nbk;
-        if (grid_c > 0x7fffffffLL) e = hipErrorInvalidValue;
-        else {
-            hipLaunchKernelGGL(observe_count_kernel<LABELLED>, dim3((unsigned)grid_c), dim3(OBS_THREADS), 0, s,
-                               cols->ref_start, cols->cig_ptr, cols->cigar, cols->seq_ptr, cols->seq, cols->qual,
-                               cols->has_qual, is_reverse, min_bq, L, nb, nbk, off, chunk_off, perm, counts, err);
-            e = hipGetLastError();
-        }
-        if (e == hipSuccess) e = hipMemcpyAsync(&err_host, err, 8, hipMemcpyDeviceToHost, s);
-    }
-    const hipError_t ef = hipFreeAsync(scratch, s);
-    if (e == hipSuccess) e = ef;
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    HIP_TRY(e);
-    if (err_host != OBS_ERR_NONE) {
-        const long long i = (long long)(err_host >> 2);
-        switch ((int)(err_host & 3)) {
-            case 0: return fail(-1, "%s: alignment %lld has a label >= n_labels (%lld)", name, i, n_labels);
-            case 1: return fail(-4, "%s: the CIGAR of alignment %lld runs past its sequence", name, i);
-            case 2: return fail(-4, "%s: the CIGAR of alignment %lld holds an unknown operation", name, i);
-            default: return fail(-1, "%s: alignment %lld reaches past the table (L = %lld)", name, i, L);
-        }
-    }
-    return 0;
+        if (grid_c > 0x7fffffffLL) return hipErrorInvalidValue;
+        hipLaunchKernelGGL(observe_count_kernel<LABELLED>, dim3((unsigned)grid_c), dim3(OBS_THREADS), 0, s,
+                           aln_view_of(cols, min_mq, min_bq), is_reverse, L, nb, nbk, off, chunk_off, perm, counts, err);
+        return hipGetLastError();
+    }));
+    char kind0[64], kind3[64];
+    snprintf(kind0, sizeof(kind0), "has a label >= n_labels (%lld)", (long long)n_labels);
+    snprintf(kind3, sizeof(kind3), "reaches past the table (L = %lld)", (long long)L);
+    return aln_walk_error(name, err_host, kind3, kind0);
 }
 
 extern "C" int mxm_observe_bases(const mxm_aln_columns *cols, const uint8_t *is_reverse, int32_t min_mq, int32_t min_bq,
@@ -2332,57 +2357,32 @@ extern "C" int mxm_new_variants(const uint8_t *cons, int64_t ld, int32_t n_rows,
     return 0;
 }
 
-static int asm_columns_ok(const char *name, const mxm_aln_columns *cols) {
-    if (cols == nullptr || cols->n_aln < 0) return fail(-1, "%s: bad arguments", name);
-    if (cols->n_aln > 0x7fffffffLL) return fail(-1, "%s: more than 2^31 - 1 alignments (%lld)", name, cols->n_aln);
-    if (cols->n_aln > 0 && (cols->ref_start == nullptr || cols->mapq == nullptr || cols->cig_ptr == nullptr ||
-                            cols->cigar == nullptr || cols->seq_ptr == nullptr || cols->seq == nullptr))
-        return fail(-1, "%s: ref_start, mapq, cig_ptr, cigar, seq_ptr and seq are required", name);
-    return 0;
-}
-
-static int asm_walk_error(const char *name, unsigned long long err_host, const char *kind3) {
-    if (err_host == OBS_ERR_NONE) return 0;
-    const long long i = (long long)(err_host >> 2);
-    switch ((int)(err_host & 3)) {
-        case 1: return fail(-4, "%s: the CIGAR of alignment %lld runs past its sequence", name, i);
-        case 2: return fail(-4, "%s: the CIGAR of alignment %lld holds an unknown operation", name, i);
-        default: snprintf(g_err, sizeof(g_err), "%s: alignment %lld %s", name, i, kind3); return -1;
-    }
-}
-
 extern "C" int mxm_first_observed(const mxm_aln_columns *cols, const int32_t *label, const int32_t *joined,
                                   int32_t n_labels, int32_t min_mq, int32_t min_bq, int64_t ref_len, const uint8_t *tied,
                                   uint8_t *cons, void *stream) {
     const char *name = "mxm_first_observed";
-    const int rc = asm_columns_ok(name, cols);
+    const int rc = aln_columns_ok(name, cols);
     if (rc) return rc;
     if (n_labels < 0 || ref_len < 0) return fail(-1, "%s: bad shape", name);
     const int64_t n = cols->n_aln, cells = (int64_t)n_labels * ref_len;
     if (n == 0 || cells == 0) return 0;
     if (label == nullptr || tied == nullptr || cons == nullptr) return fail(-1, "%s: label, tied and cons are required", name);
     hipStream_t s = (hipStream_t)stream;
-    // scratch: first[cells][8] order keys (the size of the counts tables the consensus was called from), then the error word
-    void *scratch = nullptr;
-    HIP_TRY(hipMallocAsync(&scratch, ((size_t)cells * 8 + 1) * 8, s));
-    unsigned long long *first = static_cast<unsigned long long *>(scratch), *err = first + cells * 8;
-    unsigned long long err_host = OBS_ERR_NONE;
-    hipError_t e = hipMemsetAsync(scratch, 0xff, ((size_t)cells * 8 + 1) * 8, s);
-    if (e == hipSuccess) {
-        const int64_t blocks = (n + 63) / 64;
-        hipLaunchKernelGGL(first_observed_kernel, dim3(clamp_grid((blocks + 7) / 8, num_cu() * 4)), dim3(ASM_WALK_THREADS),
-                           0, s, cols->ref_start, cols->mapq, cols->cig_ptr, cols->cigar, cols->seq_ptr, cols->seq,
-                           cols->qual, cols->has_qual, label, joined, n_labels, n, min_mq, min_bq, ref_len, tied, first, err);
+    // scratch: first[cells][8] order keys (the size of the counts tables the consensus was called from)
+    unsigned long long err_host;
+    const size_t bytes = (size_t)cells * 8 * 8;
+    HIP_TRY(aln_pass(s, bytes, &err_host, [&](void *scratch, unsigned long long *err) {
+        unsigned long long *first = static_cast<unsigned long long *>(scratch);
+        const hipError_t e = hipMemsetAsync(first, 0xff, bytes, s);                   // ASM_KEY_NONE
+        if (e != hipSuccess) return e;
+        hipLaunchKernelGGL(first_observed_kernel, dim3(clamp_grid(((n + 63) / 64 + 7) / 8, num_cu() * 4)),
+                           dim3(ASM_WALK_THREADS), 0, s, aln_view_of(cols, min_mq, min_bq), label, joined, n_labels, ref_len,
+                           tied, first, err);
         hipLaunchKernelGGL(first_resolve_kernel, dim3(clamp_grid((cells + ASM_THREADS - 1) / ASM_THREADS, num_cu() * 8)),
                            dim3(ASM_THREADS), 0, s, tied, first, cells, cons);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&err_host, err, 8, hipMemcpyDeviceToHost, s);
-    }
-    const hipError_t ef = hipFreeAsync(scratch, s);
-    if (e == hipSuccess) e = ef;
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
-    HIP_TRY(e);
-    return asm_walk_error(name, err_host, "has a label >= n_labels");
+        return hipGetLastError();
+    }));
+    return aln_walk_error(name, err_host, "has a label >= n_labels");
 }
 
 extern "C" int mxm_extend_assign(const mxm_aln_columns *cols, int32_t *label, int32_t *joined, int32_t unassigned,
@@ -2390,7 +2390,7 @@ extern "C" int mxm_extend_assign(const mxm_aln_columns *cols, int32_t *label, in
                                  int32_t min_bq, const uint32_t *newvar, int64_t ref_len, int32_t *frag_state,
                                  int32_t *moved_owner, uint32_t *n_moved, void *stream) {
     const char *name = "mxm_extend_assign";
-    int rc = asm_columns_ok(name, cols);
+    int rc = aln_columns_ok(name, cols);
     if (rc) return rc;
     asm_rows rows;
     rc = asm_rows_from(name, rows_host, n_use, n_rows, &rows);
@@ -2402,41 +2402,32 @@ extern "C" int mxm_extend_assign(const mxm_aln_columns *cols, int32_t *label, in
         (n_frag > 0 && frag_state == nullptr) || (ref_len > 0 && newvar == nullptr))
         return fail(-1, "%s: label, joined, frag, frag_state, newvar and n_moved are required", name);
     hipStream_t s = (hipStream_t)stream;
-    unsigned long long *err = nullptr, err_host = OBS_ERR_NONE;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void **>(&err), 8, s));
-    hipError_t e = hipMemsetAsync(err, 0xff, 8, s);
-    if (e == hipSuccess && n_frag > 0) e = hipMemsetAsync(frag_state, 0xff, (size_t)n_frag * 4, s);   // ASM_FRAG_EMPTY
-    if (e == hipSuccess) {
-        const int64_t blocks = (n + 63) / 64;
+    unsigned long long err_host;
+    bool lds_refused = false;
+    const hipError_t e = aln_pass(s, 0, &err_host, [&](void *, unsigned long long *err) {
+        hipError_t st = hipSuccess;
+        if (n_frag > 0) st = hipMemsetAsync(frag_state, 0xff, (size_t)n_frag * 4, s);  // ASM_FRAG_EMPTY
+        if (st != hipSuccess) return st;
+        // newvar in LDS when it fits: at most two workgroups per CU (each stages the whole table once and then walks many
+        // alignments); else read from global memory
         const size_t lds = (size_t)ref_len * 4;
-        if (lds <= ASM_LDS_MAX_BYTES) {
-            // newvar in LDS: at most two workgroups per CU (each stages the whole table once and then walks many alignments)
-            const void *kernel = reinterpret_cast<const void *>(&extend_walk_kernel<true>);
-            if (lds > 65536) e = raise_dynamic_lds(kernel, lds, name);
-            if (e != hipSuccess) {
-                hipFreeAsync(err, s);
-                return -2;
-            }
-            const int per_cu = lds * 2 <= ASM_LDS_MAX_BYTES ? 2 : 1;
-            hipLaunchKernelGGL(extend_walk_kernel<true>, dim3(clamp_grid((blocks + 7) / 8, num_cu() * per_cu)),
-                               dim3(ASM_WALK_THREADS), lds, s, cols->ref_start, cols->mapq, cols->frag, cols->cig_ptr,
-                               cols->cigar, cols->seq_ptr, cols->seq, cols->qual, cols->has_qual, label, unassigned, n,
-                               n_frag, min_mq, min_bq, newvar, ref_len, frag_state, err);
-        } else {
-            hipLaunchKernelGGL(extend_walk_kernel<false>, dim3(clamp_grid((blocks + 7) / 8, num_cu() * 4)),
-                               dim3(ASM_WALK_THREADS), 0, s, cols->ref_start, cols->mapq, cols->frag, cols->cig_ptr,
-                               cols->cigar, cols->seq_ptr, cols->seq, cols->qual, cols->has_qual, label, unassigned, n,
-                               n_frag, min_mq, min_bq, newvar, ref_len, frag_state, err);
+        const bool in_lds = lds <= ASM_LDS_MAX_BYTES;
+        auto kernel = in_lds ? &extend_walk_kernel<true> : &extend_walk_kernel<false>;
+        if (in_lds && lds > 65536) st = raise_dynamic_lds(reinterpret_cast<const void *>(kernel), lds, name);
+        if (st != hipSuccess) {
+            lds_refused = true;
+            return st;
         }
+        const int per_cu = !in_lds ? 4 : lds * 2 <= ASM_LDS_MAX_BYTES ? 2 : 1;
+        hipLaunchKernelGGL(kernel, dim3(clamp_grid(((n + 63) / 64 + 7) / 8, num_cu() * per_cu)), dim3(ASM_WALK_THREADS),
+                           in_lds ? lds : 0, s, aln_view_of(cols, min_mq, min_bq), cols->frag, label, unassigned, n_frag,
+                           newvar, ref_len, frag_state, err);
         hipLaunchKernelGGL(extend_move_kernel, dim3(clamp_grid((n + ASM_THREADS - 1) / ASM_THREADS, num_cu() * 8)),
                            dim3(ASM_THREADS), 0, s, cols->frag, n, n_frag, unassigned, rows, n_use, round, frag_state, label,
                            joined, moved_owner, n_moved);
-        e = hipGetLastError();
-        if (e == hipSuccess) e = hipMemcpyAsync(&err_host, err, 8, hipMemcpyDeviceToHost, s);
-    }
-    const hipError_t ef = hipFreeAsync(err, s);
-    if (e == hipSuccess) e = ef;
-    if (e == hipSuccess) e = hipStreamSynchronize(s);
+        return hipGetLastError();
+    });
+    if (lds_refused) return -2;                              // (raise_dynamic_lds wrote the message)
     HIP_TRY(e);
-    return asm_walk_error(name, err_host, "has a fragment index outside [0, n_frag)");
+    return aln_walk_error(name, err_host, "has a fragment index outside [0, n_frag)");
 }

@@ -8,7 +8,7 @@
 //   D / N       one gap per reference position: '-' forward, '+' reverse (pysam emits (None, rpos) for N as well)
 //   I / S       the query only;  H / P  neither
 // Bins of counts[L][16]: 0-6 forward A C G T N other '-', 7-13 reverse a c g t n other '+', 14-15 pad (never written).
-// The CIGAR is walked exactly as aln_detail::walker (aln_encode.hpp) walks it, so the two agree on query offsets.
+// The walk itself, the base rule and the error word are aln_walk.hpp's.
 //
 // Shape (everything is an integer count: the table is the same bits for any input order and any launch shape):
 //   1. bucket   alignments that count (mapq >= min_mq, ref_start >= 0) by ref_start / OBS_BUCKET; per workgroup an LDS
@@ -19,8 +19,8 @@
 //               alignment with its lanes on the bases of an op; a position past the window (a long D / N, a long
 //               read) goes to a global atomic; the window is flushed with one atomic per non-zero bin, a wave's
 //               atomics covering 4 positions x 16 bins = 256 contiguous bytes
-// Errors (the first alignment in index order wins, atomicMin): a CIGAR that runs past its sequence or holds an
-// unknown operation (-4, as mxm_aln_encode), a reference position >= L (-1: the table is too short).
+// Errors (aln_walk.hpp's word): the walk's two (-4), a reference position >= L (kind 3, -1: the table is too short), and
+// in the labelled form a label >= n_labels (kind 0, -1).
 //
 // Labelled form (LABELLED = true, mxm_observe_bases_labelled): alignment i with label[i] in [0, n_labels) is counted into
 // table counts[label[i]][L][16]; label[i] < 0 is not counted, label[i] >= n_labels is an error (-1).  The bucket key
@@ -39,16 +39,8 @@
 #define OBS_BKT_PER_WG 4096        // alignments per bucket workgroup
 #define OBS_LDS_BUCKETS 2048       // buckets an LDS histogram of step 1 holds (L up to 1 M); more: global atomics
 
-// error word: (alignment index << 2) | kind, kind 1 = CIGAR past the sequence, 2 = unknown operation, 3 = position >= L,
-// 0 = label >= n_labels (labelled form only)
-#define OBS_ERR_NONE 0xffffffffffffffffull
-
 __device__ __forceinline__ bool obs_counts(const int64_t *ref_start, const int32_t *mapq, int32_t min_mq, int64_t i) {
     return mapq[i] >= min_mq && ref_start[i] >= 0;
-}
-
-__device__ __forceinline__ void obs_error(unsigned long long *err, int64_t i, unsigned kind) {
-    atomicMin(err, ((unsigned long long)i << 2) | kind);
 }
 
 // The bucket of alignment i, or -1 when it is not counted (LABELLED: a negative label, or an error of kind 0, which
@@ -61,7 +53,7 @@ __device__ __forceinline__ int64_t obs_bucket_of(const int64_t *ref_start, const
     if (LABELLED) {
         lab = label[i];
         if (lab >= n_labels) {
-            if (MODE == 0) obs_error(err, i, 0);
+            if (MODE == 0) aln_error(err, i, 0);
             return -1;
         }
         if (lab < 0) return -1;
@@ -69,7 +61,7 @@ __device__ __forceinline__ int64_t obs_bucket_of(const int64_t *ref_start, const
     if (!obs_counts(ref_start, mapq, min_mq, i)) return -1;
     const int64_t r = ref_start[i];
     if (r >= L) {
-        if (MODE == 0) obs_error(err, i, 3);
+        if (MODE == 0) aln_error(err, i, 3);
         return -1;
     }
     return (LABELLED ? lab * nb : 0) + r / OBS_BUCKET;
@@ -171,26 +163,12 @@ __global__ __launch_bounds__(1024) void observe_scan_kernel(const unsigned long 
     }
 }
 
-__device__ __forceinline__ int obs_base_bin(uint8_t b) {
-    if (b >= 'a' && b <= 'z') b = (uint8_t)(b - 32);       // str.upper() on an ASCII character
-    switch (b) {
-        case 'A': return 0;
-        case 'C': return 1;
-        case 'G': return 2;
-        case 'T': return 3;
-        case 'N': return 4;
-        default: return 5;
-    }
-}
-
 // step 2: grid = an upper bound of the chunk count (workgroups past chunk_off[nbk] leave at once).  nb: windows of one
 // table, nbk: buckets in all (see observe_bucket_kernel).
 template <bool LABELLED>
 __global__ __launch_bounds__(OBS_THREADS) void observe_count_kernel(
-    const int64_t *__restrict__ ref_start, const int64_t *__restrict__ cig_ptr, const uint32_t *__restrict__ cigar,
-    const int64_t *__restrict__ seq_ptr, const uint8_t *__restrict__ seq, const uint8_t *__restrict__ qual,
-    const uint8_t *__restrict__ has_qual, const uint8_t *__restrict__ is_reverse, int32_t min_bq, int64_t L, int64_t nb,
-    int64_t nbk, const unsigned long long *__restrict__ off, const unsigned long long *__restrict__ chunk_off,
+    aln_view aln, const uint8_t *__restrict__ is_reverse, int64_t L, int64_t nb, int64_t nbk,
+    const unsigned long long *__restrict__ off, const unsigned long long *__restrict__ chunk_off,
     const int32_t *__restrict__ perm, uint32_t *__restrict__ counts_all, unsigned long long *err) {
     __shared__ uint32_t hist[OBS_NBIN * OBS_WIN];
     const unsigned long long g = blockIdx.x;
@@ -214,42 +192,17 @@ __global__ __launch_bounds__(OBS_THREADS) void observe_count_kernel(
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, n_wave = blockDim.x >> 6;
     for (unsigned long long a = a0 + wave; a < a1; a += n_wave) {
         const int64_t i = perm[a];
-        const int64_t s0 = seq_ptr[i], slen = seq_ptr[i + 1] - s0;
-        const bool has_q = qual != nullptr && (has_qual == nullptr || has_qual[i] != 0);
         const int rev = (is_reverse != nullptr && is_reverse[i] != 0) ? 7 : 0;
-        int64_t r = ref_start[i], q = 0;
-        for (int64_t k = cig_ptr[i]; k < cig_ptr[i + 1]; ++k) {
-            const uint32_t op = cigar[k] & 15u;
-            const int64_t len = (int64_t)(cigar[k] >> 4);
-            const bool match = op == 0 || op == 7 || op == 8, gap = op == 2 || op == 3;
-            if (op > 8) {
-                if (lane == 0) obs_error(err, i, 2);
-                break;
+        aln_walk(aln, i, lane, err, [&](bool match, int64_t r, int64_t qp, int64_t len, bool has_q) -> unsigned {
+            if (r + len > L) return 3;                       // (positions only grow: the op's last one decides)
+            for (int64_t j = lane; j < len; j += 64) {
+                const int bin = (match ? aln_base_bin(aln, has_q, qp + j) : 6) + rev;
+                const int64_t rp = r + j, w = rp - w0;
+                if (w < OBS_WIN) atomicAdd(&hist[bin * OBS_WIN + (int)w], 1u);
+                else atomicAdd(&counts[rp * 16 + bin], 1u);
             }
-            if (match && q + len > slen) {
-                if (lane == 0) obs_error(err, i, 1);
-                break;
-            }
-            if (match || gap) {
-                if (r + len > L) {                           // (positions only grow: the op's last one decides)
-                    if (lane == 0) obs_error(err, i, 3);
-                    break;
-                }
-                for (int64_t j = lane; j < len; j += 64) {
-                    int bin = 6;
-                    if (match) {
-                        const int64_t qp = s0 + q + j;
-                        bin = (has_q && (int32_t)qual[qp] < min_bq) ? 4 : obs_base_bin(seq[qp]);
-                    }
-                    bin += rev;
-                    const int64_t rp = r + j, w = rp - w0;
-                    if (w < OBS_WIN) atomicAdd(&hist[bin * OBS_WIN + (int)w], 1u);
-                    else atomicAdd(&counts[rp * 16 + bin], 1u);
-                }
-            }
-            if (match || op == 1 || op == 4) q += len;
-            if (match || gap) r += len;
-        }
+            return 0;
+        });
     }
     __syncthreads();
     // flush: thread k takes (position k / 16, bin k % 16) so that a wave's atomics cover 256 contiguous bytes

@@ -260,6 +260,47 @@ def test_errors_name_the_alignment_and_too_many_contributors():
     assert torch.cuda.is_available()
 
 
+def _tied_then(cigar, seq):
+    """Two sound alignments that disagree at position 12 (G against C: a tie for the majority consensus), then a third
+    with `cigar` over `seq`; all of contributor hap1."""
+    from mixemt_amd.alignments import AlignmentColumns
+    seqs = ["ACGT", "ACCT", seq]
+    cig = [[(0, 4)], [(0, 4)], cigar]
+    raw = numpy.frombuffer("".join(seqs).encode(), dtype=numpy.uint8)
+    return AlignmentColumns([10, 10, 10], [60, 60, 60], [0, 1, 2], numpy.cumsum([0] + [len(c) for c in cig]),
+                            [(n << 4) | op for c in cig for op, n in c], numpy.cumsum([0] + [len(q) for q in seqs]), raw,
+                            None, None, ["r0", "r1", "r2"], [0, 0, 0])
+
+
+@pytest.mark.parametrize("cigar,what", [([(0, 10)], "runs past its sequence"), ([(0, 2), (9, 1)], "holds an unknown operation")])
+def test_tie_rule_names_the_alignment_with_a_bad_cigar(cigar, what, monkeypatch):
+    """mxm_first_observed's own CIGAR errors.  Through call_consensus the labelled pileup walks the same alignments first
+    and is the one to report; with the tables counted from the two sound alignments (what a caller holding earlier
+    tables has) the tie rule's walk is the first to meet alignment 2."""
+    from mixemt_amd import assemble
+    refseq = "ACGT" * 25
+    names = ["hap1"]
+    cols = _tied_then(cigar, "ACGT")
+    cr = device_table(cols, numpy.zeros(3), names, names)
+    with pytest.raises(ValueError, match=r"failed \(-4\): mxm_observe_bases_labelled: the CIGAR of alignment 2 " + what + "$"):
+        assemble.call_consensus(refseq, cr, "hap1", 1, args_of(), strict=False)
+    sound = device_table(_subset(cols, numpy.arange(2)), numpy.zeros(2), names, names)
+    assert assemble.call_consensus(refseq, sound, "hap1", 1, args_of(), strict=False)[10:14] == "ACGT"    # G was seen first
+    tables = assemble._tables
+    monkeypatch.setattr(assemble, "_tables", lambda _cr, label, n, a, ref_len: tables(sound, label[:2].contiguous(), n, a, ref_len))
+    with pytest.raises(ValueError, match=r"failed \(-4\): mxm_first_observed: the CIGAR of alignment 2 " + what + "$"):
+        assemble.call_consensus(refseq, cr, "hap1", 1, args_of(), strict=False)
+
+
+def test_extension_names_the_alignment_with_an_unknown_operation():
+    from mixemt_amd import assemble
+    from test_gpu_observe import _one
+    bad = _one(10, [(0, 2), (9, 1)], "ACGT")
+    cr = device_table(bad, numpy.array([1]), ["hap1", "unassigned"], ["hap1", "unassigned"])
+    with pytest.raises(ValueError, match=r"failed \(-4\): mxm_extend_assign: the CIGAR of alignment 0 holds an unknown operation$"):
+        assemble.assign_reads_from_new_vars(cr, {(12, "A"): "hap1"}, args_of())
+
+
 def test_million_fragments_equal_the_restatement():
     from mixemt_amd import assemble, phylotree, preprocess, synth
     import gen_golden
