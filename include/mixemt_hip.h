@@ -58,7 +58,11 @@ extern "C" {
  * 601: mxm_observe_bases (the pileup of mixemt's variant check);
  * 602: mxm_observe_bases_labelled (one pileup per label: the per-contributor tables of mixemt's `-t` output);
  * 603: mxm_consensus, mxm_new_variants, mxm_first_observed, mxm_extend_assign (mixemt's `-b` consensus and `-x`
- * assembly extension over labelled pileups). */
+ * assembly extension over labelled pileups); still 603: mxm_samples_plan, mxm_samples_workspace_bytes,
+ * mxm_em_iter_samples, mxm_em_loop_samples (the EM loops of many samples in one batched pass over their concatenated
+ * records) were ADDED without a change to any existing signature or default, so a binding written against 603 keeps
+ * working; a binding that wants them and meets an older 603 library finds the symbols missing when it binds them
+ * (mixemt_amd/_lib.py says so and asks for a rebuild). */
 #define MXM_VERSION 603
 
 /* per-restart loop state, written by mxm_m_finalize (24 bytes); allocate it ZEROED */
@@ -381,6 +385,55 @@ int mxm_em_loop_coded(const mxm_coded *c, const double *w, int32_t H, int32_t B,
                       double *props_cur, double *ln_cur, double *ln_new, double *colsum,
                       mxm_em_state *state, double tol, int32_t max_iter, int32_t check_every,
                       void *ws, size_t ws_bytes, void *stream, mxm_em_state *state_host);
+
+/*
+ * The EM loops of MANY SAMPLES in one batched pass -- em.py:94-165 once per sample (the reference runs a cohort as one
+ * process per sample; every sample has its own rows, weights, proportions and loop state).  The samples' rows sit back to
+ * back in ONE records matrix `c`: sample s owns the rows [row0_host[s], row0_host[s + 1]), row0_host[0] = 0,
+ * row0_host[S] = c->R (HOST int64[S + 1]).  A sample is to these calls what a restart is to mxm_em_loop_coded -- one
+ * row of props / ln / colsum [S][H], one mxm_em_state, frozen once it has stopped -- that owns a disjoint set of rows.
+ * Records only: no quad dictionary (c->qrec == NULL), no dense rest (c->R_rest == 0: every row has a record, as
+ * build_em_matrix's rows do), an even H in [66, 8192], 1 <= S <= 65535.  c->wide_rows / n_wide are NOT read by the
+ * passes (a tile finds its rows with 16-bit codes from ndist); mxm_em_loop_samples still checks the list on entry, as
+ * mxm_em_loop_coded does, because the struct's other consumers rely on it.
+ *   mxm_samples_plan   HOST, no device work: cuts every sample into tiles of at most MXM_SAMPLES_TILE_ROWS
+ *                      (mixemt_hip_tuning.h) consecutive rows of that sample -- full tiles, then the remainder: the cut is
+ *                      a function of the sample's own row count and nothing else; a tile never spans two samples.
+ *                      Returns the number of tiles (-1: S < 1, row0_host[0] != 0, an empty sample or a descending
+ *                      row0_host, more than 2^31 - 1 tiles, or cap too small); tiles_host[cap] (nullable: count only)
+ *                      receives the tiles in sample order, tile0_host[S + 1] (nullable) each sample's first tile.
+ *   mxm_samples_workspace_bytes   scratch for a plan of n_tiles tiles: the tile table, one partial row of H doubles
+ *                      per tile, a fault word per tile.
+ *   mxm_em_iter_samples   one E+M pass for every unfinished sample: colsum[s][h] = T_sh as mxm_em_iter defines it, from
+ *                      sample s's rows under props[s] (em.py:80-88).  Samples with state[s].done != 0 are skipped and
+ *                      their colsum rows left untouched.  colsum[s] is the same bits on every run, whichever other samples
+ *                      share the batch and wherever s stands in it (per-tile partial rows, summed in tile order; no float
+ *                      atomics).  A row with -inf everywhere and a nonzero weight makes ITS sample's sums NaN (em.py:81-87),
+ *                      no other's.  A row without a record (ndist outside 1 .. 1024) poisons its sample's sums with NaN
+ *                      and raises state[s].error = 1; the row is never dereferenced.  The tile table (16 bytes per tile) is
+ *                      made and uploaded by every call, ordered on `stream` (the call may wait for that copy; the kernels
+ *                      are only enqueued); the caller follows it with mxm_m_finalize(B = S).
+ *   mxm_em_loop_samples   mxm_em_loop_coded over S samples -- em.py:126-143 for each: {pass; column reduce;
+ *                      mxm_m_finalize with B = S} in chunks of check_every iterations, one read-back of the states per
+ *                      chunk, until every sample is done.  Plain launches on `stream`: no persistent grid, no graph.
+ *                      tol / max_iter are one value for the batch.  Blocks; state_host[S] receives the final states.
+ *                      -1 when a sample's error was raised.
+ * mxm_em_iter_samples and mxm_em_loop_samples return -1 WITHOUT touching the device for: c->qrec != NULL, c->R_rest != 0, an odd H or one outside
+ * [66, 8192], an empty sample, a row0_host that is not ascending, row0_host[S] != c->R.
+ */
+typedef struct mxm_sample_tile {
+    int32_t sample;              /* the sample the tile belongs to */
+    int32_t count;               /* rows: 1 .. MXM_SAMPLES_TILE_ROWS */
+    int64_t first;               /* its first row in the concatenated matrix */
+} mxm_sample_tile;
+int64_t mxm_samples_plan(const int64_t *row0_host, int32_t S, mxm_sample_tile *tiles_host, int64_t cap, int32_t *tile0_host);
+size_t  mxm_samples_workspace_bytes(int64_t n_tiles, int32_t S, int32_t H);
+int mxm_em_iter_samples(const mxm_coded *c, const int64_t *row0_host, int32_t S, const double *w, const double *props,
+                        int32_t H, mxm_em_state *state, double *colsum, void *ws, size_t ws_bytes, void *stream);
+int mxm_em_loop_samples(const mxm_coded *c, const int64_t *row0_host, int32_t S, const double *w, int32_t H,
+                        double *props_cur, double *ln_cur, double *ln_new, double *colsum, mxm_em_state *state, double tol,
+                        int32_t max_iter, int32_t check_every, void *ws, size_t ws_bytes, void *stream,
+                        mxm_em_state *state_host);
 
 /*
  * The run_em inner loop for ONE rank -- em.py:126-143: repeats

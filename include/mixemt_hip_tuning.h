@@ -168,6 +168,16 @@ int mxm_set_batch_tile(int32_t bt);
  */
 int mxm_set_compact_restarts(int32_t mode);
 
+/*
+ * Kernel-shape constant of the batched pass over many samples (em_iter_samples_kernel, mxm_samples_plan): a workgroup takes
+ * one TILE of at most this many consecutive rows of one sample.  Fixed at build time -- a sample's tiles, and with them
+ * the order of its sums, must not depend on anything but its row count.  Smaller tiles spread a small batch over more of
+ * the chip and write more partial rows (H doubles per tile, read back by the column reduce); at most 64.
+ * mxm_samples_tile_rows() returns the value the loaded library was built with.
+ */
+#define MXM_SAMPLES_TILE_ROWS 32
+int mxm_samples_tile_rows(void);
+
 /* Tuning knob: rows a workgroup of the streaming kernel handles at least (grid = min(cap, R / n)). */
 int mxm_set_min_rows_per_wg(int32_t n);
 

@@ -31,6 +31,11 @@ class Coded(ctypes.Structure):
                 ("byte_rows", c_ptr), ("n_byte_rows", c_i64)]
 
 
+class SampleTile(ctypes.Structure):
+    """mxm_sample_tile (include/mixemt_hip.h): up to MXM_SAMPLES_TILE_ROWS consecutive rows of one sample."""
+    _fields_ = [("sample", c_i32), ("count", c_i32), ("first", c_i64)]
+
+
 class AlnColumns(ctypes.Structure):
     """mxm_aln_columns (include/mixemt_hip.h): alignments as columns (host pointers)."""
     _fields_ = [("n_aln", c_i64), ("n_frag", c_i64), ("ref_start", c_ptr), ("mapq", c_ptr), ("frag", c_ptr),
@@ -115,6 +120,13 @@ SIGNATURES = {
     "mxm_em_loop_coded": (ctypes.c_int, [ctypes.POINTER(Coded), c_ptr, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr,
                                          c_ptr, c_f64, c_i32, c_i32, c_ptr, c_size, c_ptr,
                                          ctypes.POINTER(EmState)]),
+    "mxm_samples_tile_rows": (ctypes.c_int, []),
+    "mxm_samples_plan": (c_i64, [c_ptr, c_i32, c_ptr, c_i64, c_ptr]),
+    "mxm_samples_workspace_bytes": (c_size, [c_i64, c_i32, c_i32]),
+    "mxm_em_iter_samples": (ctypes.c_int, [ctypes.POINTER(Coded), c_ptr, c_i32, c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_ptr,
+                                           c_size, c_ptr]),
+    "mxm_em_loop_samples": (ctypes.c_int, [ctypes.POINTER(Coded), c_ptr, c_i32, c_ptr, c_i32, c_ptr, c_ptr, c_ptr, c_ptr,
+                                           c_ptr, c_f64, c_i32, c_i32, c_ptr, c_size, c_ptr, ctypes.POINTER(EmState)]),
     "mxm_em_step": (ctypes.c_int, [c_ptr, c_i64, c_ptr, c_ptr, c_i64, c_i32, c_ptr, c_i64, c_i32,
                                    c_ptr, c_ptr, c_size, c_ptr]),
     "mxm_log_normalize": (ctypes.c_int, [c_ptr, c_i32, c_ptr, c_ptr]),

@@ -27,6 +27,8 @@
 //   coded_kernels.hpp   encode_rows_kernel, em_iter_coded_kernel (row-dictionary storage: one byte per cell + the row's distinct values)
 //   fused_coded_kernels.hpp  em_fused_coded_kernel (the whole EM loop over records in one persistent launch)
 //   fused_narrow_kernels.hpp  em_fused_narrow_kernel (the same for the refinement EM's few columns: the matrix in registers)
+//   samples_kernels.hpp em_iter_samples_kernel, samples_colreduce_kernel (the EM iteration of many samples in one launch: a tile of
+//                       one sample's rows per workgroup)
 //   aln_encode.hpp      HOST code: mxm_aln_encode, the batched alignment front end (process_reads + reduce_reads + row order)
 //   observe_kernels.hpp observe_bucket_kernel, observe_count_kernel (the pileup of the variant check: observe.py:56-86)
 //   assemble_kernels.hpp  consensus_kernel, new_variants_kernel, first_observed_kernel, extend_walk_kernel, extend_move_kernel
@@ -65,6 +67,7 @@
 #include "fused_cols_kernels.hpp"
 #include "fused_coded_kernels.hpp"
 #include "fused_narrow_kernels.hpp"
+#include "samples_kernels.hpp"
 #include "exchange.hpp"
 #include "aln_walk.hpp"
 #include "observe_kernels.hpp"
@@ -1954,6 +1957,190 @@ extern "C" int mxm_em_loop_coded(const mxm_coded *c, const double *w, int32_t H,
     }
     return em_loop_impl(nullptr, 0, nullptr, 0, w, c->R, H, B, props_cur, ln_cur, ln_new, colsum, state, tol, max_iter,
                         check_every, ws, ws_bytes, stream, state_host, false, c);
+}
+
+// ---- the EM loops of many samples in one batched pass (samples_kernels.hpp) ------------------------------------------
+extern "C" int mxm_samples_tile_rows(void) { return MXM_SAMPLES_TILE_ROWS; }
+
+extern "C" int64_t mxm_samples_plan(const int64_t *row0_host, int32_t S, mxm_sample_tile *tiles_host, int64_t cap,
+                                    int32_t *tile0_host) {
+    if (row0_host == nullptr || S < 1) return fail(-1, "mxm_samples_plan: bad arguments%s (S=%lld)", "", S);
+    if (row0_host[0] != 0) return fail(-1, "mxm_samples_plan: row0[0] must be 0%s (it is %lld)", "", row0_host[0]);
+    constexpr int64_t K = MXM_SAMPLES_TILE_ROWS;
+    int64_t n = 0;
+    for (int32_t s = 0; s < S; ++s) {
+        const int64_t rows = row0_host[s + 1] - row0_host[s];
+        if (rows <= 0)
+            return fail(-1, "mxm_samples_plan: row0 must ascend and no sample may be empty%s (sample %lld has %lld rows)", "", s, rows);
+        if (tile0_host != nullptr) tile0_host[s] = (int32_t)n;
+        const int64_t nt = (rows + K - 1) / K;
+        if (n + nt > 0x7fffffffll) return fail(-1, "mxm_samples_plan: more than 2^31 - 1 tiles%s", "");
+        if (tiles_host != nullptr) {
+            if (n + nt > cap) return fail(-1, "mxm_samples_plan: room for %s%lld tiles, sample %lld needs more", "", cap, s);
+            for (int64_t i = 0; i < nt; ++i) {
+                const int64_t left = rows - i * K;
+                tiles_host[n + i] = mxm_sample_tile{s, (int32_t)(left < K ? left : K), row0_host[s] + i * K};
+            }
+        }
+        n += nt;
+    }
+    if (tile0_host != nullptr) tile0_host[S] = (int32_t)n;
+    return n;
+}
+
+// scratch layout: [tile table][first tile of every sample, S + 1][fault word per tile][partial rows, one per tile]
+struct samples_ws {
+    mxm_sample_tile *tiles;
+    int32_t *tile0;
+    int *chk;
+    double *partial;
+    size_t bytes;
+};
+static samples_ws samples_layout(void *ws, int64_t n_tiles, int S, int H) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    samples_ws L;
+    char *base = static_cast<char *>(ws);
+    size_t at = 0;
+    L.tiles = reinterpret_cast<mxm_sample_tile *>(base + at);
+    at += up((size_t)n_tiles * sizeof(mxm_sample_tile));
+    L.tile0 = reinterpret_cast<int32_t *>(base + at);
+    at += up((size_t)(S + 1) * sizeof(int32_t));
+    L.chk = reinterpret_cast<int *>(base + at);
+    at += up((size_t)n_tiles * sizeof(int));
+    L.partial = reinterpret_cast<double *>(base + at);
+    at += (size_t)n_tiles * (size_t)part_ld(H) * sizeof(double);
+    L.bytes = at;
+    return L;
+}
+extern "C" size_t mxm_samples_workspace_bytes(int64_t n_tiles, int32_t S, int32_t H) {
+    if (n_tiles <= 0 || S <= 0 || H <= 0) return 0;
+    return samples_layout(nullptr, n_tiles, (int)S, (int)H).bytes;
+}
+
+// Everything the two entry points refuse before they touch the device; *n_tiles_out = the plan's size.
+static int samples_check(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, const char *who, int64_t *n_tiles_out) {
+    if (c == nullptr || row0_host == nullptr || S < 1 || S > 65535)
+        return fail(-1, "%s: bad arguments (S = %lld; 1 .. 65535 samples)", who, S);
+    if (c->R <= 0 || c->rec == nullptr || c->rec_off == nullptr || c->ndist == nullptr)
+        return fail(-1, "%s: coded matrix arrays missing (rows %lld)", who, c->R);
+    if ((H & 1) != 0 || H < 66 || H > 8192) return fail(-1, "%s: H = %lld: an even width in [66, 8192] is required", who, H);
+    if (c->qrec != nullptr) return fail(-1, "%s: a quad dictionary is attached; the batched pass reads the records only", who);
+    if (c->R_rest != 0) return fail(-1, "%s: %lld rows without a record (the dense rest): such a sample runs on its own", who, c->R_rest);
+    if (c->n_wide < 0 || (c->n_wide > 0 && c->wide_rows == nullptr)) return fail(-1, "%s: n_wide > 0 needs wide_rows", who);
+    const int64_t n_tiles = mxm_samples_plan(row0_host, S, nullptr, 0, nullptr);
+    if (n_tiles < 0) return -1;                           // (the plan's message stands)
+    if (row0_host[S] != c->R) return fail(-1, "%s: row0[S] = %lld, the matrix has %lld rows", who, row0_host[S], c->R);
+    *n_tiles_out = n_tiles;
+    return 0;
+}
+
+// the plan into the workspace, ordered on `stream` (from pageable memory: the runtime has taken the bytes when the call returns)
+static int samples_upload_plan(const int64_t *row0_host, int S, int64_t n_tiles, const samples_ws &L, hipStream_t stream) {
+    static thread_local std::vector<mxm_sample_tile> tiles;
+    static thread_local std::vector<int32_t> tile0;
+    tiles.resize((size_t)n_tiles);
+    tile0.resize((size_t)S + 1);
+    if (mxm_samples_plan(row0_host, S, tiles.data(), n_tiles, tile0.data()) != n_tiles) return -1;
+    HIP_TRY(hipMemcpyAsync(L.tiles, tiles.data(), (size_t)n_tiles * sizeof(mxm_sample_tile), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(L.tile0, tile0.data(), ((size_t)S + 1) * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    return 0;
+}
+
+// one pass for every unfinished sample: the tiles, then each sample's column reduce
+static int samples_enqueue_pass(const mxm_coded *c, const double *w, const double *props, int H, int S, int64_t n_tiles,
+                                const samples_ws &L, mxm_em_state *state, double *colsum, hipStream_t stream) {
+    const int ldc = coded_ld(H);
+    const int nch = (ldc / 4 + SAMPLES_THREADS - 1) / SAMPLES_THREADS;
+    const int64_t ldpart = part_ld(H);
+    switch (nch) {
+#define SMP_CASE(n) case n: hipLaunchKernelGGL((em_iter_samples_kernel<n, 4>), dim3((unsigned)n_tiles), dim3(SAMPLES_THREADS), 0, stream, c->rec, c->rec_off, c->ndist, ldc, w, props, H, (const mxm_sample_tile *)L.tiles, L.partial, ldpart, L.chk, (const mxm_em_state *)state); break;
+        SMP_CASE(1) SMP_CASE(2) SMP_CASE(3) SMP_CASE(4) SMP_CASE(5) SMP_CASE(6) SMP_CASE(7) SMP_CASE(8)
+#undef SMP_CASE
+        default: return fail(-1, "mxm_em_iter_samples: H=%s%lld outside the kernel's range", "", H);
+    }
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(samples_colreduce_kernel, dim3((H + SAMPLES_COLRED_THREADS - 1) / SAMPLES_COLRED_THREADS, S),
+                       dim3(SAMPLES_COLRED_THREADS), 0, stream, (const double *)L.partial, ldpart, (const int32_t *)L.tile0,
+                       (const int *)L.chk, H, colsum, state);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mxm_em_iter_samples(const mxm_coded *c, const int64_t *row0_host, int32_t S, const double *w, const double *props,
+                                   int32_t H, mxm_em_state *state, double *colsum, void *ws, size_t ws_bytes, void *stream) {
+    MXM_ENTER();
+    int64_t n_tiles = 0;
+    const int rc = samples_check(c, row0_host, S, H, "mxm_em_iter_samples", &n_tiles);
+    if (rc != 0) return rc;
+    if (props == nullptr || colsum == nullptr || state == nullptr) return fail(-1, "mxm_em_iter_samples: bad arguments%s", "");
+    if (ws == nullptr || ws_bytes < mxm_samples_workspace_bytes(n_tiles, S, H) || (reinterpret_cast<uintptr_t>(ws) & 15))
+        return fail(-1, "mxm_em_iter_samples: workspace too small (or not 16-byte aligned)%s", "");
+    const samples_ws L = samples_layout(ws, n_tiles, (int)S, (int)H);
+    const int urc = samples_upload_plan(row0_host, (int)S, n_tiles, L, (hipStream_t)stream);
+    if (urc != 0) return urc;
+    return samples_enqueue_pass(c, w, props, (int)H, (int)S, n_tiles, L, state, colsum, (hipStream_t)stream);
+}
+
+extern "C" int mxm_em_loop_samples(const mxm_coded *c, const int64_t *row0_host, int32_t S, const double *w, int32_t H,
+                                   double *props_cur, double *ln_cur, double *ln_new, double *colsum, mxm_em_state *state,
+                                   double tol, int32_t max_iter, int32_t check_every, void *ws, size_t ws_bytes, void *stream,
+                                   mxm_em_state *state_host) {
+    MXM_ENTER();
+    int64_t n_tiles = 0;
+    const int rc = samples_check(c, row0_host, S, H, "mxm_em_loop_samples", &n_tiles);
+    if (rc != 0) return rc;
+    if (props_cur == nullptr || ln_cur == nullptr || ln_new == nullptr || colsum == nullptr || state == nullptr || state_host == nullptr)
+        return fail(-1, "mxm_em_loop_samples: bad arguments%s", "");
+    if (ws == nullptr || ws_bytes < mxm_samples_workspace_bytes(n_tiles, S, H) || (reinterpret_cast<uintptr_t>(ws) & 15))
+        return fail(-1, "mxm_em_loop_samples: workspace too small (or not 16-byte aligned)%s", "");
+    if (check_every < 1) check_every = 1;
+    if (T.progress != nullptr && check_every > T.progress_every) check_every = T.progress_every;
+    hipStream_t s = (hipStream_t)stream;
+    const samples_ws L = samples_layout(ws, n_tiles, (int)S, (int)H);
+    {
+        // mxm_coded's contract, checked once as mxm_em_loop_coded does: wide_rows lists exactly the rows with 16-bit codes
+        // (the passes here find them from ndist; the struct's other readers take the list's word)
+        unsigned long long *chk = reinterpret_cast<unsigned long long *>(L.partial), host[2] = {0, 0};
+        HIP_TRY(hipMemsetAsync(chk, 0, 2 * sizeof(unsigned long long), s));
+        hipLaunchKernelGGL(coded_validate_kernel, dim3(clamp_grid((c->R + 255) / 256, num_cu() * 4)), dim3(256), 0, s, c->ndist, c->R,
+                           c->wide_rows, c->n_wide, chk);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(host, chk, sizeof(host), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        if (host[1] != 0 || (long long)host[0] != (long long)c->n_wide)
+            return fail(-1, "mxm_em_loop_samples: wide_rows must list exactly the rows with more than 256 values, ascending "
+                            "%s(%lld such rows, n_wide = %lld)", "", (long long)host[0], (long long)c->n_wide);
+    }
+    const int urc = samples_upload_plan(row0_host, (int)S, n_tiles, L, s);
+    if (urc != 0) return urc;
+    HIP_TRY(hipMemcpyAsync(state_host, state, sizeof(mxm_em_state) * S, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    auto running = [&]() {
+        int n = 0;
+        for (int b = 0; b < S; ++b) n += (state_host[b].done == 0) ? 1 : 0;
+        return n;
+    };
+    while (max_iter > 0 && running() > 0) {
+        // a chunk ends where its first unfinished sample reaches max_iter at the latest (kernels of a finished sample are
+        // no-ops, so running past a sample's stop changes nothing -- it only costs launches)
+        int64_t n = check_every, most_left = 0;
+        for (int b = 0; b < S; ++b)
+            if (state_host[b].done == 0) most_left = std::max<int64_t>(most_left, (int64_t)max_iter - state_host[b].iters);
+        if (most_left > 0 && most_left < n) n = most_left;
+        for (int64_t it = 0; it < n; ++it) {
+            const int prc = samples_enqueue_pass(c, w, props_cur, (int)H, (int)S, n_tiles, L, state, colsum, s);
+            if (prc != 0) return prc;
+            const int frc = mxm_m_finalize(colsum, ln_cur, ln_new, props_cur, H, S, tol, max_iter, state, s);
+            if (frc != 0) return frc;
+        }
+        HIP_TRY(hipMemcpyAsync(state_host, state, sizeof(mxm_em_state) * S, hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        for (int b = 0; b < S; ++b)
+            if (state_host[b].error != 0)
+                return fail(-1, "mxm_em_loop_samples: sample %s%lld has a row without a record (ndist outside 1 .. 1024)", "", b);
+        if (T.progress != nullptr) T.progress(state_host, S, T.progress_user);
+    }
+    return 0;
 }
 
 extern "C" int mxm_em_loop_f32(const float *P, int64_t ldp, const double *w, int64_t R, int32_t H, int32_t B,

@@ -771,6 +771,177 @@ def run_em_ex(read_hap_mat, weights, args, inits=None, want_read_mix=True, stora
     return res
 
 
+class SampleBatch(object):
+    """
+    The rows of many samples back to back in ONE records matrix, for the batched loop (mxm_em_loop_samples):
+        rec                        the record buffer every entry's offsets point into
+        rec_off, ndist, wts [R]    the concatenated rows (an entry may REPEAT another's offsets: the restarts of one sample
+                                   share its records, nothing is copied)
+        row0 [S + 1] numpy int64   entry s owns the rows [row0[s], row0[s + 1])
+    """
+
+    def __init__(self, rec, rec_off, ndist, wts, row0, n_haps):
+        self.lib = _lib.load()
+        self.dev = rec.device
+        self.rec, self.rec_off, self.ndist, self.wts = rec, rec_off.contiguous(), ndist.contiguous(), wts.contiguous()
+        self.row0 = numpy.ascontiguousarray(row0, dtype=numpy.int64)
+        self.n_entries, self.n_rows, self.n_haps = len(self.row0) - 1, int(self.row0[-1]), int(n_haps)
+        if self.rec_off.numel() != self.n_rows or self.ndist.numel() != self.n_rows or self.wts.numel() != self.n_rows:
+            raise ValueError("rec_off / ndist / weights do not match row0")
+        nd_h = self.ndist.cpu().numpy()
+        self.wide = torch.from_numpy(numpy.flatnonzero(nd_h > 256)).to(self.dev)
+        n_wide = int(self.wide.numel())
+        self.coded = _lib.Coded(self.rec.data_ptr(), self.rec_off.data_ptr(), self.ndist.data_ptr(), self.n_rows,
+                                None, 0, None, 0, self.wide.data_ptr() if n_wide else None, n_wide)
+        self.row0_ptr = self.row0.ctypes.data_as(ctypes.c_void_p)
+        self.n_tiles = int(self.lib.mxm_samples_plan(self.row0_ptr, self.n_entries, None, 0, None))
+        if self.n_tiles < 0:
+            raise ValueError("mxm_samples_plan failed: %s" % self.lib.mxm_last_error().decode("utf-8", "replace"))
+        self.ws_bytes = int(self.lib.mxm_samples_workspace_bytes(self.n_tiles, self.n_entries, self.n_haps))
+        self.ws = device_empty((self.ws_bytes // 8 + 1,), torch.float64, self.dev, "the batched loop's workspace")
+
+    def em_iter(self, props, state, colsum):
+        """Enqueue one pass for every unfinished entry (mxm_em_iter_samples): colsum[s] <- entry s's unscaled sums."""
+        _lib.check(self.lib.mxm_em_iter_samples(ctypes.byref(self.coded), self.row0_ptr, self.n_entries, self.wts.data_ptr(),
+                                                props.data_ptr(), self.n_haps, ptr(state), colsum.data_ptr(),
+                                                self.ws.data_ptr(), self.ws_bytes, current_stream()), "mxm_em_iter_samples")
+
+    def em_loop(self, inits, tolerance, max_iter, check_every=16):
+        """em_loop for every entry at once: inits [S][H] linear.  Returns (ln_cur, ln_new, [(done, iters, l1)])."""
+        ln0, p0 = log_inits(inits)
+        if ln0.shape != (self.n_entries, self.n_haps):
+            raise ValueError("inits must be [%d][%d]" % (self.n_entries, self.n_haps))
+        props_cur = torch.from_numpy(p0).to(self.dev)
+        ln_cur = torch.from_numpy(ln0).to(self.dev)
+        ln_new = ln_cur.clone()
+        colsum = torch.zeros_like(props_cur)
+        state = new_state(self.n_entries, self.dev)
+        host_state = (_lib.EmState * self.n_entries)()
+        _lib.check(self.lib.mxm_em_loop_samples(ctypes.byref(self.coded), self.row0_ptr, self.n_entries, self.wts.data_ptr(),
+                                                self.n_haps, props_cur.data_ptr(), ln_cur.data_ptr(), ln_new.data_ptr(),
+                                                colsum.data_ptr(), state.data_ptr(), float(tolerance), int(max_iter),
+                                                int(check_every), self.ws.data_ptr(), self.ws_bytes, current_stream(),
+                                                host_state), "mxm_em_loop_samples")
+        return ln_cur, ln_new, [(s.done, s.iters, s.l1) for s in host_state]
+
+
+def _fold_runs(ln_next):
+    """collect_result's proportions: exp(mean of the runs' LOG proportions), in run order (em.py:155, :163)."""
+    res = ln_next[0].copy()
+    for run in range(1, len(ln_next)):
+        res += ln_next[run]
+    if len(ln_next) > 1:
+        res /= len(ln_next)
+    return numpy.exp(res)
+
+
+def draw_inits_many(n_samples, n_haps, n_multi=1, alpha=1.0):
+    """run_em_many's initial proportions: init_props (em.py:23-36, :123) from numpy's global legacy stream, sample after
+    sample, n_multi draws each -- the order a Python loop of run_em over the samples consumes the stream in.  A list of
+    [n_multi][H] arrays."""
+    return [numpy.stack([init_props(n_haps, alpha=alpha) for _ in range(n_multi)]) for _ in range(n_samples)]
+
+
+def run_em_many(samples, args, inits=None, tables=None):
+    """
+    run_em's loop (em.py:94-165) for MANY samples in one batched device pass (mxm_em_loop_samples) instead of a Python
+    loop of run_em_ex over them -- opt-in; run_em / run_em_ex are unchanged.
+    samples: a list of (matrix, weights), every matrix over the same haplogroups, ALL of one kind:
+        (row_ptr, site, obs)    a sample's CSR observations; `tables` (preprocess.HapVarTables) is then required and the
+                                rows of all samples are built as records in ONE call (preprocess.build_em_records_many)
+        preprocess.CodedMatrix  records; all samples must share one record buffer (views of one build:
+                                cm.rows(lo, hi) of build_em_records_many's matrix)
+        a dense [R][H] matrix   (numpy or device) encoded with the others in one mxm_encode_rows call
+    Returns one dict per sample: props ([H], theta_{k+1} folded over the restarts as run_em folds them), ln_theta_k
+    ([n_multi][H], log theta_k), run_props ([n_multi][H]; batch route: also their logs, ln_theta_next), iters / done / l1
+    (per restart), inits, and route: "batch", or
+    "single" for a sample with rows the encoder left without a record (more than 1024 distinct values: none from
+    build_em_matrix) -- that one runs through run_em_ex on its own.
+    args.tolerance / max_iter / init_alpha hold for the whole batch.  args.n_multi > 1: every sample takes n_multi
+    entries of the batch over the SAME records (offsets repeated, not copied).
+    inits: None = drawn as run_em draws them, from numpy's global legacy stream, sample after sample (n_multi draws
+    each): sample s alone at the same position of the stream reproduces its own draw; or a list with inits[s] [H] or
+    [n_multi][H].
+    Not here: the posterior matrix, votes, contributors (per sample: run_em_ex(records=...) / assign), the quad
+    dictionary, several GPUs, fp32 storage.
+    """
+    from . import preprocess
+    lib = _lib.load()
+    dev = require_gpu()
+    n_multi = int(args.n_multi)
+    if not samples or n_multi < 1:
+        raise ValueError("run_em_many: no samples")
+    mats = [m for m, _ in samples]
+    # ---- one records matrix over all samples ----
+    single_input = [None] * len(samples)               # what run_em_ex gets if the sample has to run on its own
+    if all(isinstance(m, preprocess.CodedMatrix) for m in mats):
+        if any(m.rec.data_ptr() != mats[0].rec.data_ptr() for m in mats):
+            raise ValueError("run_em_many: records of different builds cannot share a batch (build them with "
+                             "preprocess.build_em_records_many)")
+        n_haps, rec = mats[0].n_haps, mats[0].rec
+        rec_off, ndist = torch.cat([m.rec_off for m in mats]), torch.cat([m.ndist for m in mats])
+        counts = [m.n_rows for m in mats]
+        single_input = [dict(read_hap_mat=None, records=m) for m in mats]
+    elif all(isinstance(m, (tuple, list)) and len(m) == 3 for m in mats):
+        if tables is None:
+            raise ValueError("run_em_many: CSR samples need tables=")
+        cm, row0 = preprocess.build_em_records_many(tables, mats)
+        n_haps, rec, rec_off, ndist = cm.n_haps, cm.rec, cm.rec_off, cm.ndist
+        counts = list(numpy.diff(row0))
+        single_input = [dict(read_hap_mat=None, records=cm.rows(row0[i], row0[i + 1])) for i in range(len(mats))]
+    elif not any(isinstance(m, (tuple, list, preprocess.CodedMatrix)) for m in mats):
+        dense = [as_device(m, torch.float64, dev) for m in mats]
+        if any(d.dim() != 2 or d.shape[1] != dense[0].shape[1] or d.shape[0] < 1 for d in dense):
+            raise ValueError("run_em_many: every sample needs a 2-D matrix of at least one row over the same haplogroups")
+        n_haps = int(dense[0].shape[1])
+        counts = [int(d.shape[0]) for d in dense]
+        if not lib.mxm_linear_supported(n_haps):
+            raise ValueError("run_em_many: records need H in [65, 8192]")
+        plan = EmPlan(torch.cat(dense), numpy.ones(sum(counts)), storage="coded", keep_log_matrix=False)
+        rec, rec_off, ndist = plan._coded_keep[:3]
+        single_input = [dict(read_hap_mat=d, storage="coded") for d in dense]
+    else:
+        raise ValueError("run_em_many: the samples must be all CSR triples, all CodedMatrix or all dense matrices")
+    wts = [as_device(w, torch.float64, dev).reshape(-1) for _, w in samples]
+    if any(int(w.numel()) != int(n) for w, n in zip(wts, counts)):
+        raise ValueError("run_em_many: weights do not match the samples' rows")
+    # ---- initial proportions: run_em's draws, sample after sample ----
+    if inits is None:
+        inits = draw_inits_many(len(samples), n_haps, n_multi, args.init_alpha)
+    inits = [numpy.ascontiguousarray(numpy.atleast_2d(numpy.asarray(i, dtype=numpy.float64))) for i in inits]
+    if len(inits) != len(samples) or any(i.shape != (n_multi, n_haps) for i in inits):
+        raise ValueError("run_em_many: inits[s] must be [n_multi][H] for every sample")
+    # ---- samples with rows the encoder left dense run on their own ----
+    nd_h = ndist.cpu().numpy()
+    starts = numpy.concatenate([[0], numpy.cumsum(counts)]).astype(numpy.int64)
+    alone = [bool((nd_h[starts[i]:starts[i + 1]] <= 0).any()) for i in range(len(samples))]
+    results = [None] * len(samples)
+    batch_ids = [i for i in range(len(samples)) if not alone[i]]
+    if batch_ids:
+        def rows_of(x, i):
+            return x[int(starts[i]):int(starts[i + 1])]
+        whole = len(batch_ids) == len(samples) and n_multi == 1
+        b_off = rec_off if whole else torch.cat([rows_of(rec_off, i) for i in batch_ids for _ in range(n_multi)])
+        b_nd = ndist if whole else torch.cat([rows_of(ndist, i) for i in batch_ids for _ in range(n_multi)])
+        b_w = torch.cat([wts[i] for i in batch_ids for _ in range(n_multi)])
+        row0 = numpy.concatenate([[0], numpy.cumsum([counts[i] for i in batch_ids for _ in range(n_multi)])])
+        batch = SampleBatch(rec, b_off, b_nd, b_w, row0, n_haps)
+        ln_cur, ln_new, states = batch.em_loop(numpy.concatenate([inits[i] for i in batch_ids]), args.tolerance, args.max_iter)
+        ln_k, ln_next = ln_cur.cpu().numpy(), ln_new.cpu().numpy()
+        for j, i in enumerate(batch_ids):
+            sl = slice(j * n_multi, (j + 1) * n_multi)
+            results[i] = {"props": _fold_runs(ln_next[sl]), "ln_theta_k": ln_k[sl].copy(), "ln_theta_next": ln_next[sl].copy(),
+                          "run_props": numpy.exp(ln_next[sl]),
+                          "iters": [st[1] for st in states[sl]], "done": [st[0] for st in states[sl]],
+                          "l1": [st[2] for st in states[sl]], "inits": inits[i], "route": "batch"}
+    for i in range(len(samples)):
+        if alone[i]:
+            res = run_em_ex(weights=samples[i][1], args=args, inits=inits[i], want_read_mix=False, **single_input[i])
+            res["route"] = "single"
+            results[i] = res
+    return results
+
+
 def run_em(read_hap_mat, weights, args):
     """
     Drop-in for mixemt.em.run_em (em.py:94-165): returns (props, read_mix) --

@@ -808,6 +808,30 @@ def build_em_records_device(tables, row_ptr, site, obs, dense=False, cap=None, r
     return (cm, mat) if dense else cm
 
 
+def build_em_records_many(tables, samples_csr, cap=None):
+    """
+    The rows of MANY samples as ONE CodedMatrix, for em.run_em_many: samples_csr is a list of (row_ptr, site, obs) CSR
+    triples (numpy or device), one per sample, all over the same `tables` -- so the concatenated CSR goes through
+    mxm_build_em_records in ONE call and the build kernels need no change.  Returns (cm, row0): sample s owns the rows
+    [row0[s], row0[s + 1]) of cm (row0: numpy int64[S + 1]); cm.rows(row0[s], row0[s + 1]) is the sample's own matrix
+    (a view: the records are not copied).
+    """
+    if not samples_csr:
+        raise ValueError("no samples")
+    ptrs, sites, obss, row0, nnz = [], [], [], [0], 0
+    for row_ptr, site, obs in samples_csr:
+        rp = numpy.asarray(row_ptr.cpu() if isinstance(row_ptr, torch.Tensor) else row_ptr, dtype=numpy.int64)
+        if rp.ndim != 1 or rp.size < 2 or rp[0] != 0:
+            raise ValueError("every sample needs at least one row (row_ptr[0] = 0)")
+        ptrs.append(rp[(1 if ptrs else 0):] + nnz)
+        nnz += int(rp[-1])
+        row0.append(row0[-1] + rp.size - 1)
+        sites.append(numpy.asarray(site.cpu() if isinstance(site, torch.Tensor) else site).astype(numpy.uint16, copy=False)[:int(rp[-1])])
+        obss.append(numpy.asarray(obs.cpu() if isinstance(obs, torch.Tensor) else obs).astype(numpy.uint8, copy=False)[:int(rp[-1])])
+    cm = build_em_records_device(tables, numpy.concatenate(ptrs), numpy.concatenate(sites), numpy.concatenate(obss), cap=cap)
+    return cm, numpy.asarray(row0, dtype=numpy.int64)
+
+
 build_em_matrix_device.last_fallback = 0       # rows the marker kernel handed to the lookup-table kernel, last call
 
 
