@@ -49,7 +49,7 @@ def build(force=False, defines=(), verbose=False, out=None):
     global LIB
     if out is not None:
         LIB = os.path.abspath(out)
-    flags = ["--offload-arch=%s" % ARCH, "-O3", "-std=c++17", "-shared", "-fPIC",
+    flags = ["--offload-arch=%s" % ARCH, "-O3", "-std=c++17", "-shared", "-fPIC", "-Werror=format",
              "-I" + os.path.join(_ROOT, "include"), "-I" + os.path.dirname(SRC)]
     flags += ["-D%s" % d for d in defines]
     stamp = LIB + ".stamp"

@@ -186,10 +186,10 @@ static int aln_encode_impl(const mxm_aln_columns *c, const int32_t *site_of_pos,
         if (n_threads > 16) n_threads = 16;
     }
     for (int64_t i = 0; i < n_aln; ++i)
-        if (c->frag[i] < 0 || c->frag[i] >= n_frag) return fail(-1, "mxm_aln_encode: fragment index of alignment %s%lld outside [0, n_frag)", "", i);
+        if (c->frag[i] < 0 || c->frag[i] >= n_frag) return fail(-1, "mxm_aln_encode: fragment index of alignment %lld outside [0, n_frag)", (long long)i);
     for (int32_t s = 0; s < n_sites; ++s)
         if (site_pos[s] < 0 || site_pos[s] >= ref_len || site_of_pos[site_pos[s]] != s || (s > 0 && site_pos[s] <= site_pos[s - 1]))
-            return fail(-1, "mxm_aln_encode: site_pos / site_of_pos do not describe the same ascending site list%s (site %lld)", "", s);
+            return fail(-1, "mxm_aln_encode: site_pos / site_of_pos do not describe the same ascending site list (site %lld)", (long long)s);
     std::vector<int32_t> next_site((size_t)ref_len + 1);
     {
         int32_t s = n_sites;
@@ -225,7 +225,7 @@ static int aln_encode_impl(const mxm_aln_columns *c, const int32_t *site_of_pos,
     });
     for (int t = 0; t < n_threads; ++t)
         if (bad[t] >= 0)
-            return fail(-4, "mxm_aln_encode: alignment %s%lld has a CIGAR that runs past its sequence or an unknown operation", "", bad[t]);
+            return fail(-4, "mxm_aln_encode: alignment %lld has a CIGAR that runs past its sequence or an unknown operation", (long long)bad[t]);
     stamp("count");
     // fragment ranges; a fragment's place in the reference's dict = the first alignment that gave it an observation
     std::vector<int64_t> f_cnt((size_t)n_frag, 0), f_first((size_t)n_frag, -1), a_off((size_t)n_aln);
@@ -547,15 +547,15 @@ static int aln_encode_impl(const mxm_aln_columns *c, const int32_t *site_of_pos,
 extern "C" int mxm_aln_encode(const mxm_aln_columns *cols, const int32_t *site_of_pos, int64_t ref_len,
                               const int64_t *site_pos, int32_t n_sites, int32_t min_mq, int32_t min_bq, int32_t n_threads,
                               mxm_aln_enc **out) {
-    if (out == nullptr) return fail(-1, "mxm_aln_encode: out is NULL%s", "");
+    if (out == nullptr) return fail(-1, "mxm_aln_encode: out is NULL");
     *out = nullptr;
     if (cols == nullptr || cols->n_aln < 0 || cols->n_frag < 0 || site_of_pos == nullptr || site_pos == nullptr || ref_len <= 0 ||
         n_sites < 0 || n_sites > 65536)
-        return fail(-1, "mxm_aln_encode: bad arguments%s", "");
+        return fail(-1, "mxm_aln_encode: bad arguments");
     if (cols->n_aln > 0 && (cols->ref_start == nullptr || cols->mapq == nullptr || cols->frag == nullptr || cols->cig_ptr == nullptr ||
                             cols->seq_ptr == nullptr || (cols->cig_ptr[cols->n_aln] > 0 && cols->cigar == nullptr) ||
                             (cols->seq_ptr[cols->n_aln] > 0 && cols->seq == nullptr)))
-        return fail(-1, "mxm_aln_encode: alignment columns missing%s", "");
+        return fail(-1, "mxm_aln_encode: alignment columns missing");
     mxm_aln_enc *res = nullptr;
     try {
         res = new mxm_aln_enc();
@@ -573,7 +573,7 @@ extern "C" int mxm_aln_encode(const mxm_aln_columns *cols, const int32_t *site_o
 }
 
 extern "C" int mxm_aln_sizes_of(const mxm_aln_enc *e, mxm_aln_sizes *s) {
-    if (e == nullptr || s == nullptr) return fail(-1, "mxm_aln_sizes_of: NULL argument%s", "");
+    if (e == nullptr || s == nullptr) return fail(-1, "mxm_aln_sizes_of: NULL argument");
     s->n_rows = (int64_t)e->weights.size();
     s->nnz = e->row_ptr.empty() ? 0 : e->row_ptr.back();
     s->n_grouped = (int64_t)e->group_frag.size();
@@ -591,7 +591,7 @@ static inline void aln_copy_out(const std::vector<V> &v, P *dst) {
 
 extern "C" int mxm_aln_fetch(const mxm_aln_enc *e, int64_t *row_ptr, uint16_t *site, uint8_t *obs, int64_t *weights,
                              int64_t *group_ptr, int64_t *group_frag, int64_t *dropped, char *text, int64_t *text_off) {
-    if (e == nullptr) return fail(-1, "mxm_aln_fetch: NULL handle%s", "");
+    if (e == nullptr) return fail(-1, "mxm_aln_fetch: NULL handle");
     aln_copy_out(e->row_ptr, row_ptr);
     const int64_t n_rows = (int64_t)e->weights.size();
     if (site != nullptr || obs != nullptr || text != nullptr) {
@@ -615,7 +615,7 @@ extern "C" int mxm_aln_fetch(const mxm_aln_enc *e, int64_t *row_ptr, uint16_t *s
 }
 
 extern "C" int mxm_aln_fetch_fragments(const mxm_aln_enc *e, int64_t *frag_id, int64_t *frag_ptr, uint16_t *site, uint8_t *obs) {
-    if (e == nullptr) return fail(-1, "mxm_aln_fetch_fragments: NULL handle%s", "");
+    if (e == nullptr) return fail(-1, "mxm_aln_fetch_fragments: NULL handle");
     aln_copy_out(e->frag_id, frag_id);
     int64_t at = 0;
     for (size_t k = 0; k < e->frag_id.size(); ++k) {

@@ -204,7 +204,7 @@ static int bam_read_impl(const char *path, int n_threads, mxm_bam *out) {
             aln_detail::run_threads(n_threads, work);                    // (aln_encode.hpp: no exception leaves a worker thread)
         }
         for (int t = 0; t < n_threads; ++t)
-            if (bad[t] >= 0) return fail(-4, "mxm_bam_read: BGZF block %s%lld does not inflate to its recorded size and CRC", "", bad[t]);
+            if (bad[t] >= 0) return fail(-4, "mxm_bam_read: BGZF block %lld does not inflate to its recorded size and CRC", (long long)bad[t]);
     }
     stamp("inflate");
     // ---- BAM header ------------------------------------------------------------------------------------------
@@ -238,7 +238,7 @@ static int bam_read_impl(const char *path, int n_threads, mxm_bam *out) {
         const int32_t ref_id = (int32_t)le32(r);
         const uint32_t l_read_name = r[8], n_cigar_op = le16(r + 12), l_seq = le32(r + 16);
         if (32ull + l_read_name + 4ull * n_cigar_op + ((uint64_t)l_seq + 1) / 2 + (uint64_t)l_seq > (uint64_t)block_size || l_read_name == 0)
-            return fail(-4, "mxm_bam_read: alignment record %s%lld is inconsistent", "", (long long)out->n_records_total - 1);
+            return fail(-4, "mxm_bam_read: alignment record %lld is inconsistent", (long long)out->n_records_total - 1);
         if (ref_id >= 0) {
             recs.push_back(r);
             n_cig += n_cigar_op;
@@ -309,7 +309,7 @@ static int bam_read_impl(const char *path, int n_threads, mxm_bam *out) {
         aln_detail::run_threads(n_threads, fill);
     }
     for (size_t t = 0; t < too_long.size(); ++t)
-        if (too_long[t] >= 0) return fail(-4, "mxm_bam_read: alignment %s%lld keeps its CIGAR in a CG tag (more than 65535 operations)", "", too_long[t]);
+        if (too_long[t] >= 0) return fail(-4, "mxm_bam_read: alignment %lld keeps its CIGAR in a CG tag (more than 65535 operations)", (long long)too_long[t]);
     for (int64_t i = 0; i < n; ++i) out->any_qual = out->any_qual || out->has_qual[i] != 0;
     stamp("columns");
     // ---- fragments: equal read names share an index, numbered by first appearance ---------------------------
@@ -387,7 +387,7 @@ static int bam_read_impl(const char *path, int n_threads, mxm_bam *out) {
 }
 
 extern "C" int mxm_bam_read(const char *path, int32_t n_threads, mxm_bam **out) {
-    if (out == nullptr || path == nullptr) return fail(-1, "mxm_bam_read: NULL argument%s", "");
+    if (out == nullptr || path == nullptr) return fail(-1, "mxm_bam_read: NULL argument");
     *out = nullptr;
     mxm_bam *res = nullptr;
     try {
@@ -406,7 +406,7 @@ extern "C" int mxm_bam_read(const char *path, int32_t n_threads, mxm_bam **out) 
 }
 
 extern "C" int mxm_bam_sizes_of(const mxm_bam *b, mxm_bam_sizes *s) {
-    if (b == nullptr || s == nullptr) return fail(-1, "mxm_bam_sizes_of: NULL argument%s", "");
+    if (b == nullptr || s == nullptr) return fail(-1, "mxm_bam_sizes_of: NULL argument");
     s->n_aln = (int64_t)b->ref_start.size();
     s->n_frag = (int64_t)b->name_off.size() - 1;
     s->n_cigar = (int64_t)b->cigar.size();
@@ -419,7 +419,7 @@ extern "C" int mxm_bam_sizes_of(const mxm_bam *b, mxm_bam_sizes *s) {
 }
 
 extern "C" int mxm_bam_columns(const mxm_bam *b, mxm_aln_columns *cols) {
-    if (b == nullptr || cols == nullptr) return fail(-1, "mxm_bam_columns: NULL argument%s", "");
+    if (b == nullptr || cols == nullptr) return fail(-1, "mxm_bam_columns: NULL argument");
     cols->n_aln = (int64_t)b->ref_start.size();
     cols->n_frag = (int64_t)b->name_off.size() - 1;
     cols->ref_start = b->ref_start.data();
@@ -435,7 +435,7 @@ extern "C" int mxm_bam_columns(const mxm_bam *b, mxm_aln_columns *cols) {
 }
 
 extern "C" int mxm_bam_fetch_names(const mxm_bam *b, char *names, int64_t *name_off, int32_t *ref_id, uint16_t *flag) {
-    if (b == nullptr) return fail(-1, "mxm_bam_fetch_names: NULL handle%s", "");
+    if (b == nullptr) return fail(-1, "mxm_bam_fetch_names: NULL handle");
     if (names != nullptr && !b->names.empty()) memcpy(names, b->names.data(), b->names.size());
     if (name_off != nullptr) memcpy(name_off, b->name_off.data(), b->name_off.size() * sizeof(int64_t));
     if (ref_id != nullptr && !b->ref_id.empty()) memcpy(ref_id, b->ref_id.data(), b->ref_id.size() * sizeof(int32_t));

@@ -1,5 +1,5 @@
 // common.hpp -- part of libmixemt_hip.so (gfx950); included by mixemt_hip.hip only.
-// Error plumbing, device query, wave / workgroup reductions shared by every kernel.
+// Device query, wave / workgroup reductions shared by every kernel (the error plumbing: error.hpp).
 #ifndef MIXEMT_COMMON_HPP
 #define MIXEMT_COMMON_HPP
 
@@ -16,20 +16,7 @@ struct mxm_slots {
 };
 #define MXM_LINEAR_MIN_H 65        // below this the log-space kernel is used
 
-// ------------------------------------------------------------------------------------------
-// error plumbing
-// ------------------------------------------------------------------------------------------
-static thread_local char g_err[512] = "";
-
-static int fail(int code, const char *fmt, const char *a = "", long long b = 0, long long c = 0) {
-    snprintf(g_err, sizeof(g_err), fmt, a, b, c);
-    return code;
-}
-#define HIP_TRY(expr)                                                                        \
-    do {                                                                                     \
-        hipError_t e_ = (expr);                                                              \
-        if (e_ != hipSuccess) return fail(-2, "HIP error: %s (line %lld)", hipGetErrorString(e_), __LINE__); \
-    } while (0)
+#include "error.hpp"              // g_err, fail, HIP_TRY (host only)
 
 // CUs of the calling thread's CURRENT device, cached per device (one host thread per GPU may share the process).
 #define MXM_MAX_DEVICES 64

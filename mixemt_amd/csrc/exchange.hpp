@@ -191,8 +191,8 @@ extern "C" size_t mxm_exchange_handle_bytes(void) { return sizeof(hipIpcMemHandl
 extern "C" int mxm_exchange_create(int32_t world, int32_t rank, int64_t n_doubles, mxm_exchange **out, void *handle_out) {
     if (out == nullptr || handle_out == nullptr || world < 1 || world > MXM_EXCHANGE_MAX_WORLD || rank < 0 || rank >= world ||
         n_doubles < 1)
-        return fail(-1, "mxm_exchange_create: 1..%s%lld ranks, a rank among them and a slot size required", "",
-                    (long long)MXM_EXCHANGE_MAX_WORLD);
+        return fail(-1, "mxm_exchange_create: 1..%d ranks, a rank among them and a slot size required",
+                    MXM_EXCHANGE_MAX_WORLD);
     mxm_exchange *x = new mxm_exchange();
     x->world = world;
     x->rank = rank;
@@ -212,7 +212,7 @@ extern "C" int mxm_exchange_create(int32_t world, int32_t rank, int64_t n_double
     if (const char *fr = getenv("MXM_EXCHANGE_FAIL_RANK")) {
         if (fr[0] != '\0' && atoi(fr) == rank) {
             delete x;
-            return fail(-2, "mxm_exchange_create: failure injected on rank %s%lld (MXM_EXCHANGE_FAIL_RANK)", "", (long long)rank);
+            return fail(-2, "mxm_exchange_create: failure injected on rank %d (MXM_EXCHANGE_FAIL_RANK)", rank);
         }
     }
     const char *rf = getenv("MXM_EXCHANGE_REFUSE_FINE");
@@ -229,7 +229,7 @@ extern "C" int mxm_exchange_create(int32_t world, int32_t rank, int64_t n_double
             (void)hipGetLastError();
             if (fine) continue;
             delete x;
-            return fail(-2, "mxm_exchange_create: cannot allocate %s%lld bytes", "", (long long)bytes);
+            return fail(-2, "mxm_exchange_create: cannot allocate %lld bytes", (long long)bytes);
         }
         e = hipMemset(ptr, 0, bytes);
         if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -254,7 +254,7 @@ extern "C" int mxm_exchange_create(int32_t world, int32_t rank, int64_t n_double
 }
 
 extern "C" int mxm_exchange_connect(mxm_exchange *x, const void *handles) {
-    if (x == nullptr || handles == nullptr) return fail(-1, "mxm_exchange_connect: NULL argument%s", "");
+    if (x == nullptr || handles == nullptr) return fail(-1, "mxm_exchange_connect: NULL argument");
     const unsigned char *h = static_cast<const unsigned char *>(handles);
     for (int p = 0; p < x->world; ++p) {
         if (p == x->rank || x->peers.base[p] != nullptr) continue;
@@ -264,7 +264,7 @@ extern "C" int mxm_exchange_connect(mxm_exchange *x, const void *handles) {
         const hipError_t e = hipIpcOpenMemHandle(&ptr, handle, hipIpcMemLazyEnablePeerAccess);
         if (e != hipSuccess || ptr == nullptr) {
             (void)hipGetLastError();
-            return fail(-2, "mxm_exchange_connect: cannot map rank %s%lld's buffer (%lld)", "", (long long)p, (long long)e);
+            return fail(-2, "mxm_exchange_connect: cannot map rank %d's buffer (%lld)", p, (long long)e);
         }
         x->peers.base[p] = static_cast<unsigned char *>(ptr);
         x->opened[p] = true;
@@ -273,9 +273,9 @@ extern "C" int mxm_exchange_connect(mxm_exchange *x, const void *handles) {
 }
 
 extern "C" int mxm_exchange_push(mxm_exchange *x, const double *colsum, int64_t n, void *stream) {
-    if (x == nullptr || colsum == nullptr || n < 1 || n > x->cap) return fail(-1, "mxm_exchange_push: bad arguments%s", "");
+    if (x == nullptr || colsum == nullptr || n < 1 || n > x->cap) return fail(-1, "mxm_exchange_push: bad arguments");
     for (int p = 0; p < x->world; ++p)
-        if (x->peers.base[p] == nullptr) return fail(-1, "mxm_exchange_push: rank %s%lld is not connected", "", (long long)p);
+        if (x->peers.base[p] == nullptr) return fail(-1, "mxm_exchange_push: rank %d is not connected", p);
     int grid = (int)((n + MXM_EXCHANGE_THREADS * 4 - 1) / (MXM_EXCHANGE_THREADS * 4));
     if (grid < 1) grid = 1;
     if (grid > 64) grid = 64;
@@ -287,7 +287,7 @@ extern "C" int mxm_exchange_push(mxm_exchange *x, const double *colsum, int64_t 
 
 extern "C" int mxm_exchange_pull(mxm_exchange *x, double *colsum, int64_t n, mxm_em_state *state, int32_t nb, void *stream) {
     if (x == nullptr || colsum == nullptr || n < 1 || n > x->cap || nb < 0 || nb > MXM_EXCHANGE_THREADS)
-        return fail(-1, "mxm_exchange_pull: bad arguments%s", "");
+        return fail(-1, "mxm_exchange_pull: bad arguments");
     int grid = (int)((n + MXM_EXCHANGE_THREADS * 4 - 1) / (MXM_EXCHANGE_THREADS * 4));
     if (grid < 1) grid = 1;
     if (grid > 64) grid = 64;
@@ -299,9 +299,9 @@ extern "C" int mxm_exchange_pull(mxm_exchange *x, double *colsum, int64_t n, mxm
 
 extern "C" int mxm_exchange_reduce(mxm_exchange *x, double *colsum, int64_t n, mxm_em_state *state, int32_t nb, void *stream) {
     if (x == nullptr || colsum == nullptr || n < 1 || n > x->cap || nb < 0 || nb > MXM_EXCHANGE_THREADS)
-        return fail(-1, "mxm_exchange_reduce: bad arguments%s", "");
+        return fail(-1, "mxm_exchange_reduce: bad arguments");
     for (int p = 0; p < x->world; ++p)
-        if (x->peers.base[p] == nullptr) return fail(-1, "mxm_exchange_reduce: rank %s%lld is not connected", "", (long long)p);
+        if (x->peers.base[p] == nullptr) return fail(-1, "mxm_exchange_reduce: rank %d is not connected", p);
     int grid = (int)((n + MXM_EXCHANGE_THREADS * 4 - 1) / (MXM_EXCHANGE_THREADS * 4));
     if (grid < 1) grid = 1;
     if (grid > MXM_EXCHANGE_MAX_GRID) grid = MXM_EXCHANGE_MAX_GRID;
@@ -312,7 +312,7 @@ extern "C" int mxm_exchange_reduce(mxm_exchange *x, double *colsum, int64_t n, m
 }
 
 extern "C" int mxm_exchange_info(const mxm_exchange *x, int32_t *fine_grained, int64_t *bytes) {
-    if (x == nullptr) return fail(-1, "mxm_exchange_info: NULL handle%s", "");
+    if (x == nullptr) return fail(-1, "mxm_exchange_info: NULL handle");
     if (fine_grained != nullptr) *fine_grained = x->fine_grained ? 1 : 0;
     if (bytes != nullptr) *bytes = (int64_t)x->bytes;
     return 0;

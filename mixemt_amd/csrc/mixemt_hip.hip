@@ -12,7 +12,8 @@
 //
 // One translation unit; the kernels live in headers beside this file
 // (DESIGN.md section 4 has the roofline of each):
-//   common.hpp          error plumbing, reductions
+//   error.hpp           HOST code: g_err, fail (printf-checked), HIP_TRY -- also included by tests/native/bam_reader_harness.cpp
+//   common.hpp          device query, reductions
 //   build_kernels.hpp   build_em_matrix_kernel (byte table, L2/MALL: any alphabet, any width)
 //   build_lut_kernels.hpp  build_lut_kernel (hit/miss by LDS lookup)
 //   build_sparse_kernels.hpp  build_sparse_kernel (the row from the haplogroups' markers: one in-order sum per distinct cell value)
@@ -33,7 +34,9 @@
 //   observe_kernels.hpp observe_bucket_kernel, observe_count_kernel (the pileup of the variant check: observe.py:56-86)
 //   assemble_kernels.hpp  consensus_kernel, new_variants_kernel, first_observed_kernel, extend_walk_kernel, extend_move_kernel
 //                       (consensus sequences and assembly extension over labelled pileups: assemble.py:431-585)
-// This file: the host side of the C ABI (shape checks, grid sizing, dispatch, the loop driver).
+// This file: the host side of the C ABI (shape checks, grid sizing, dispatch, the loop drivers).  Every refusal goes
+// through fail / HIP_TRY / RC_TRY, a runtime chunk count reaches its kernel instance through dispatch_width<MAX>, the
+// checks several entry points share are dynamic_lds_ok, rest_check, coded_check, samples_check, records_lists_check.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -139,6 +142,35 @@ static hipError_t raise_dynamic_lds(const void *kernel, size_t bytes, const char
                  hipGetErrorString(e));
     return e;
 }
+// The dynamic LDS of a launch: refused above 150 KiB where the caller has no other kernel for the width ("<who>: H=<H>
+// <too_wide>", -1), opted into above 60 KiB (-2 when the runtime refuses), else 0.
+static int dynamic_lds_ok(const void *kernel, size_t bytes, const char *name, const char *who = nullptr, int H = 0,
+                          const char *too_wide = nullptr) {
+    if (too_wide != nullptr && bytes > 150 * 1024) return fail(-1, "%s: H=%d %s", who, H, too_wide);
+    if (bytes > 60 * 1024 && raise_dynamic_lds(kernel, bytes, name) != hipSuccess) return -2;
+    return 0;
+}
+
+// A step that returns a status of the ABI: the first one that is not 0 ends the calling function.
+#define RC_TRY(expr)                                                                         \
+    do {                                                                                     \
+        const int rc_ = (expr);                                                              \
+        if (rc_ != 0) return rc_;                                                            \
+    } while (0)
+
+// From a runtime width to a template instance: calls f(std::integral_constant<int, n>{}) where 1 <= n <= MAX and
+// returns whether it did (the caller keeps its own "outside the kernel's range" message).  Exactly the instances
+// 1 .. MAX of what f launches are compiled; f narrows them further with `if constexpr` on its argument's value.
+template <int MAX, typename F>
+static bool dispatch_width(int n, F &&f) {
+    if constexpr (MAX < 1) {
+        return false;
+    } else {
+        if (n != MAX) return dispatch_width<MAX - 1>(n, f);
+        f(std::integral_constant<int, MAX>{});
+        return true;
+    }
+}
 
 extern "C" int mxm_version(void) { return MXM_VERSION; }
 extern "C" const char *mxm_last_error(void) { return g_err; }
@@ -216,11 +248,11 @@ extern "C" int mxm_build_em_matrix(const uint8_t *E, int64_t lde, const double *
                                    const double *lmiss, const int64_t *row_ptr, const uint16_t *site,
                                    const uint8_t *obs, int64_t R, int32_t H, int32_t S, double *M,
                                    int64_t ldm, void *stream) {
-    if (R < 0 || H <= 0 || S <= 0) return fail(-1, "mxm_build_em_matrix: bad shape R=%s%lld H=%lld", "", R, H);
+    if (R < 0 || H <= 0 || S <= 0) return fail(-1, "mxm_build_em_matrix: bad shape R=%lld H=%d", (long long)R, H);
     if (lde < (((int64_t)H + 7) & ~(int64_t)7) || (lde & 7) != 0 || (reinterpret_cast<uintptr_t>(E) & 7) != 0)
-        return fail(-1, "mxm_build_em_matrix: E must be 8-byte aligned with lde a multiple of 8 and >= H rounded up to 8%s (lde=%lld)", "", lde);
-    if (ldm < H) return fail(-1, "mxm_build_em_matrix: ldm < H%s", "");
-    if (S > 65536) return fail(-1, "mxm_build_em_matrix: more than 65536 variant sites%s", "");
+        return fail(-1, "mxm_build_em_matrix: E must be 8-byte aligned with lde a multiple of 8 and >= H rounded up to 8 (lde=%lld)", (long long)lde);
+    if (ldm < H) return fail(-1, "mxm_build_em_matrix: ldm < H");
+    if (S > 65536) return fail(-1, "mxm_build_em_matrix: more than 65536 variant sites");
     if (R == 0) return 0;
     const int grid = clamp_grid(R, num_cu() * 8);
     const int vec_ok = ((ldm & 1) == 0) && ((reinterpret_cast<uintptr_t>(M) & 15) == 0);
@@ -230,16 +262,29 @@ extern "C" int mxm_build_em_matrix(const uint8_t *E, int64_t lde, const double *
     return 0;
 }
 
-static int launch_build_lut(int nt, int grid, hipStream_t s, const uint8_t *E, int64_t lde, int64_t e_bytes,
-                            const double *lhit, const double *lmiss, const uint8_t *obsmap, const int64_t *row_ptr,
-                            const uint16_t *site, const uint8_t *obs, const int64_t *order, int64_t R, int H, double *M,
-                            int64_t ldm, int vec_ok, int compact = 0) {
-    switch (nt) {
-#define BL_CASE(n) case n: hipLaunchKernelGGL((build_lut_kernel<n, LUT_CPL>), dim3(grid), dim3(LUT_THREADS), 0, s, E, lde, e_bytes, lhit, lmiss, obsmap, row_ptr, site, obs, order, R, H, M, ldm, vec_ok, compact); break;
-        BL_CASE(1) BL_CASE(2) BL_CASE(3) BL_CASE(4) BL_CASE(5) BL_CASE(6) BL_CASE(7) BL_CASE(8)
-#undef BL_CASE
-        default: return 1;
-    }
+// Both LUT builds after their own first check.  `compact`: row order[i] of the input goes to row i of M (the rows
+// entry; else every row to its own place, and a width refusal names the build that takes any width).
+static int build_lut_impl(const char *who, const uint8_t *Ecode, int64_t lde, const double *lhit,
+                          const double *lmiss, const uint8_t *obsmap, const int64_t *row_ptr, const uint16_t *site,
+                          const uint8_t *obs, const int64_t *order, int64_t R, int32_t H, int32_t S, double *M, int64_t ldm,
+                          int compact, hipStream_t s) {
+    if (H > 8192) return fail(-1, "%s: more than 8192 haplogroups (H=%d)%s", who, H, compact ? "" : ": use mxm_build_em_matrix");
+    if (lde < (((int64_t)H + 7) & ~(int64_t)7) || (lde & 7) != 0 || (reinterpret_cast<uintptr_t>(Ecode) & 7) != 0)
+        return fail(-1, "%s: Ecode must be 8-byte aligned with lde a multiple of 8 and >= H rounded up to 8 (lde=%lld)", who, (long long)lde);
+    if (ldm < H) return fail(-1, "%s: ldm < H", who);
+    if (S > 65536 || (int64_t)S * lde >= ((int64_t)1 << 31))
+        return fail(-1, "%s: table of %d x %lld bytes exceeds one buffer descriptor", who, S, (long long)lde);
+    if (R == 0) return 0;
+    const int grid = clamp_grid(R, num_cu() * 8);
+    const int nt = (H + LUT_THREADS * LUT_CPL - 1) / (LUT_THREADS * LUT_CPL);
+    const int vec_ok = ((ldm & 1) == 0) && ((reinterpret_cast<uintptr_t>(M) & 15) == 0);
+    const bool ok = dispatch_width<8>(nt, [&](auto n) {
+        constexpr int NT = decltype(n)::value;
+        hipLaunchKernelGGL((build_lut_kernel<NT, LUT_CPL>), dim3(grid), dim3(LUT_THREADS), 0, s, Ecode, lde, (int64_t)S * lde, lhit,
+                           lmiss, obsmap, row_ptr, site, obs, order, R, (int)H, M, ldm, vec_ok, compact);
+    });
+    if (!ok) return fail(-1, "%s: H=%d outside the kernel's range", who, H);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 
@@ -247,22 +292,9 @@ extern "C" int mxm_build_em_matrix_lut(const uint8_t *Ecode, int64_t lde, const 
                                        const uint8_t *obsmap, const int64_t *row_ptr, const uint16_t *site,
                                        const uint8_t *obs, const int64_t *order, int64_t R, int32_t H, int32_t S,
                                        double *M, int64_t ldm, void *stream) {
-    if (R < 0 || H <= 0 || S <= 0) return fail(-1, "mxm_build_em_matrix_lut: bad shape R=%s%lld H=%lld", "", R, H);
-    if (H > 8192) return fail(-1, "mxm_build_em_matrix_lut: more than 8192 haplogroups%s (H=%lld): use mxm_build_em_matrix", "", H);
-    if (lde < (((int64_t)H + 7) & ~(int64_t)7) || (lde & 7) != 0 || (reinterpret_cast<uintptr_t>(Ecode) & 7) != 0)
-        return fail(-1, "mxm_build_em_matrix_lut: Ecode must be 8-byte aligned with lde a multiple of 8 and >= H rounded up to 8%s (lde=%lld)", "", lde);
-    if (ldm < H) return fail(-1, "mxm_build_em_matrix_lut: ldm < H%s", "");
-    if (S > 65536 || (int64_t)S * lde >= ((int64_t)1 << 31))
-        return fail(-1, "mxm_build_em_matrix_lut: table of %s%lld x %lld bytes exceeds one buffer descriptor", "", S, lde);
-    if (R == 0) return 0;
-    const int grid = clamp_grid(R, num_cu() * 8);
-    const int nt = (H + LUT_THREADS * LUT_CPL - 1) / (LUT_THREADS * LUT_CPL);
-    const int vec_ok = ((ldm & 1) == 0) && ((reinterpret_cast<uintptr_t>(M) & 15) == 0);
-    if (launch_build_lut(nt, grid, (hipStream_t)stream, Ecode, lde, (int64_t)S * lde, lhit, lmiss, obsmap, row_ptr, site, obs,
-                         order, R, (int)H, M, ldm, vec_ok) != 0)
-        return fail(-1, "mxm_build_em_matrix_lut: H=%s%lld outside the kernel's range", "", H);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    if (R < 0 || H <= 0 || S <= 0) return fail(-1, "mxm_build_em_matrix_lut: bad shape R=%lld H=%d", (long long)R, H);
+    return build_lut_impl("mxm_build_em_matrix_lut", Ecode, lde, lhit, lmiss, obsmap, row_ptr, site, obs,
+                          order, R, H, S, M, ldm, 0, (hipStream_t)stream);
 }
 
 // the listed rows into a COMPACT matrix: row rows[i] of the input -> row i of M_out (build_em_records_device's slabs)
@@ -270,22 +302,9 @@ extern "C" int mxm_build_em_matrix_lut_rows(const uint8_t *Ecode, int64_t lde, c
                                             const uint8_t *obsmap, const int64_t *row_ptr, const uint16_t *site,
                                             const uint8_t *obs, const int64_t *rows, int64_t n_rows, int32_t H, int32_t S,
                                             double *M_out, int64_t ldm, void *stream) {
-    if (n_rows < 0 || H <= 0 || S <= 0 || rows == nullptr) return fail(-1, "mxm_build_em_matrix_lut_rows: bad arguments%s", "");
-    if (H > 8192) return fail(-1, "mxm_build_em_matrix_lut_rows: more than 8192 haplogroups%s (H=%lld)", "", H);
-    if (lde < (((int64_t)H + 7) & ~(int64_t)7) || (lde & 7) != 0 || (reinterpret_cast<uintptr_t>(Ecode) & 7) != 0)
-        return fail(-1, "mxm_build_em_matrix_lut_rows: Ecode must be 8-byte aligned with lde a multiple of 8 and >= H rounded up to 8%s (lde=%lld)", "", lde);
-    if (ldm < H) return fail(-1, "mxm_build_em_matrix_lut_rows: ldm < H%s", "");
-    if (S > 65536 || (int64_t)S * lde >= ((int64_t)1 << 31))
-        return fail(-1, "mxm_build_em_matrix_lut_rows: table of %s%lld x %lld bytes exceeds one buffer descriptor", "", S, lde);
-    if (n_rows == 0) return 0;
-    const int grid = clamp_grid(n_rows, num_cu() * 8);
-    const int nt = (H + LUT_THREADS * LUT_CPL - 1) / (LUT_THREADS * LUT_CPL);
-    const int vec_ok = ((ldm & 1) == 0) && ((reinterpret_cast<uintptr_t>(M_out) & 15) == 0);
-    if (launch_build_lut(nt, grid, (hipStream_t)stream, Ecode, lde, (int64_t)S * lde, lhit, lmiss, obsmap, row_ptr, site, obs, rows,
-                         n_rows, (int)H, M_out, ldm, vec_ok, 1) != 0)
-        return fail(-1, "mxm_build_em_matrix_lut_rows: H=%s%lld outside the kernel's range", "", H);
-    HIP_TRY(hipGetLastError());
-    return 0;
+    if (n_rows < 0 || H <= 0 || S <= 0 || rows == nullptr) return fail(-1, "mxm_build_em_matrix_lut_rows: bad arguments");
+    return build_lut_impl("mxm_build_em_matrix_lut_rows", Ecode, lde, lhit, lmiss, obsmap, row_ptr, site, obs, rows, n_rows, H, S,
+                          M_out, ldm, 1, (hipStream_t)stream);
 }
 
 // The records of a slab of rows that were coded from their dense form (mxm_encode_rows over a compact side matrix) take
@@ -305,7 +324,7 @@ extern "C" int mxm_scatter_records(const int64_t *rows, int64_t n, const int64_t
                                    int64_t base, int64_t *rec_off, int32_t *ndist, double *rowmax, void *stream) {
     if (n < 0 || (n > 0 && (rows == nullptr || sub_off == nullptr || sub_nd == nullptr || sub_rm == nullptr || rec_off == nullptr ||
                             ndist == nullptr || rowmax == nullptr)))
-        return fail(-1, "mxm_scatter_records: bad arguments%s", "");
+        return fail(-1, "mxm_scatter_records: bad arguments");
     if (n == 0) return 0;
     hipLaunchKernelGGL(scatter_records_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, rows, n, sub_off,
                        sub_nd, sub_rm, base, rec_off, ndist, rowmax);
@@ -335,8 +354,8 @@ static int build_sparse_impl(const char *who, const uint8_t *maj, const double *
                              const int64_t *row_ptr, const uint16_t *site, const uint8_t *obs, const int64_t *order,
                              int64_t R, int32_t H, int32_t S, double *M, int64_t ldm, const spb_records *out,
                              int64_t *fallback, int64_t *n_fallback, hipStream_t s) {
-    if (R < 0 || H <= 0 || S <= 0) return fail(-1, "%s: bad shape R=%lld H=%lld", who, R, H);
-    if (H > 8192) return fail(-1, "%s: more than 8192 haplogroups (H=%lld): use mxm_build_em_matrix", who, H);
+    if (R < 0 || H <= 0 || S <= 0) return fail(-1, "%s: bad shape R=%lld H=%d", who, (long long)R, H);
+    if (H > 8192) return fail(-1, "%s: more than 8192 haplogroups (H=%d): use mxm_build_em_matrix", who, H);
     if (M != nullptr && ldm < H) return fail(-1, "%s: ldm < H", who);
     if (maj == nullptr || mk_ptr == nullptr || fallback == nullptr || n_fallback == nullptr)
         return fail(-1, "%s: marker tables and the fallback list are required", who);
@@ -365,41 +384,38 @@ static int build_sparse_impl(const char *who, const uint8_t *maj, const double *
     const int grid_long = clamp_grid((R + SPB_LONG_CHUNK - 1) / SPB_LONG_CHUNK, num_cu() * 4 * 2);
     spb_records none = {};
     const spb_records rec = out != nullptr ? *out : none;
-#define SPB_ARGS maj, lhit, lmiss, mk_ptr, mk_hap, mk_base, row_ptr, site, obs, order, R, (int)H, M, ldm, vec_ok, fallback, reinterpret_cast<unsigned long long *>(n_fallback), maxd, rec
-#define SPB_LAUNCH(n, p) do { if (out != nullptr) hipLaunchKernelGGL((build_sparse_kernel<n, p, true, 1>), dim3(grid), dim3(SPB_THREADS), 0, s, SPB_ARGS, long_too, 0); \
-                          else hipLaunchKernelGGL((build_sparse_kernel<n, p, false, 1>), dim3(grid), dim3(SPB_THREADS), 0, s, SPB_ARGS, long_too, 0); } while (0)
+    // W = 1: rows of up to 64 observations; W = 2: the rows of 65 .. 128 (below)
+    auto launch = [&](auto kernel, int nwg, int max_distinct, int long_rows_too, int long_entries) {
+        hipLaunchKernelGGL(kernel, dim3(nwg), dim3(SPB_THREADS), 0, s, maj, lhit, lmiss, mk_ptr, mk_hap, mk_base, row_ptr, site, obs,
+                           order, R, (int)H, M, ldm, vec_ok, fallback, reinterpret_cast<unsigned long long *>(n_fallback), max_distinct,
+                           rec, long_rows_too, long_entries);
+    };
     // (only the instances of the column-range count this build runs with are compiled: the other three quarters of them
     // were a third of the library's build time)
-#define SPB_CASE(n) case n: if constexpr (SPB_PASSES == 1) { if constexpr (n <= 7) SPB_LAUNCH(n, 1); else return fail(-1, "%s: one pass covers H <= 3584", who); } else if constexpr (SPB_PASSES == 2) SPB_LAUNCH(n, 2); else if constexpr (SPB_PASSES == 3) SPB_LAUNCH(n, 3); else SPB_LAUNCH(n, 4); break;
-    switch (nch) {
-        SPB_CASE(1) SPB_CASE(2) SPB_CASE(3) SPB_CASE(4) SPB_CASE(5) SPB_CASE(6) SPB_CASE(7) SPB_CASE(8)
-        SPB_CASE(9) SPB_CASE(10) SPB_CASE(11) SPB_CASE(12) SPB_CASE(13) SPB_CASE(14) SPB_CASE(15) SPB_CASE(16)
-        default: return fail(-1, "%s: H=%lld outside the kernel's range", who, H);
-    }
+    constexpr int P = SPB_PASSES < 4 ? SPB_PASSES : 4;
+    bool one_pass_too_wide = false;
+    const bool ok = dispatch_width<16>(nch, [&](auto n) {
+        constexpr int N = decltype(n)::value;
+        if constexpr (P == 1 && N > 7) one_pass_too_wide = true;
+        else if (out != nullptr) launch(build_sparse_kernel<N, P, true, 1>, grid, maxd, long_too, 0);
+        else launch(build_sparse_kernel<N, P, false, 1>, grid, maxd, long_too, 0);
+    });
+    if (one_pass_too_wide) return fail(-1, "%s: one pass covers H <= 3584", who);
+    if (!ok) return fail(-1, "%s: H=%d outside the kernel's range", who, H);
     HIP_TRY(hipGetLastError());
     if (long_too != 0) {
         // the rows of 65 .. 128 observations (merged mates, long reads): 128-bit masks, one column range per 512 haplogroups
         // and a table of 1024 slots (build_sparse_kernels.hpp, W = 2); its grid looks at the rows 64 at a time
-#define SPB_ARGS_LONG maj, lhit, lmiss, mk_ptr, mk_hap, mk_base, row_ptr, site, obs, order, R, (int)H, M, ldm, vec_ok, fallback, reinterpret_cast<unsigned long long *>(n_fallback), maxd_long, rec
-#define SPB_LONG(n, p) case n: if (out != nullptr) hipLaunchKernelGGL((build_sparse_kernel<n, p, true, 2>), dim3(grid_long), dim3(SPB_THREADS), 0, s, SPB_ARGS_LONG, 0, T.sparse_long_entries); \
-                               else hipLaunchKernelGGL((build_sparse_kernel<n, p, false, 2>), dim3(grid_long), dim3(SPB_THREADS), 0, s, SPB_ARGS_LONG, 0, T.sparse_long_entries); break;
-        switch (nch) {
 #ifndef SPB_LONG_KPP
 #define SPB_LONG_KPP 2                // 512-haplogroup chunks per column range of the long rows' instance (1: 34.9, 2: 34.5, 4: 36.5 ms
                                       // per 10^6 paired-end fragments before the walk over a long row's further entries was fixed)
 #endif
-#define SPB_LP(n) SPB_LONG(n, ((n + SPB_LONG_KPP - 1) / SPB_LONG_KPP))
-            SPB_LP(1) SPB_LP(2) SPB_LP(3) SPB_LP(4) SPB_LP(5) SPB_LP(6) SPB_LP(7) SPB_LP(8)
-            SPB_LP(9) SPB_LP(10) SPB_LP(11) SPB_LP(12) SPB_LP(13) SPB_LP(14) SPB_LP(15) SPB_LP(16)
-#undef SPB_LP
-            default: break;
-        }
-#undef SPB_LONG
-#undef SPB_ARGS_LONG
+        (void)dispatch_width<16>(nch, [&](auto n) {
+            constexpr int N = decltype(n)::value, PL = (N + SPB_LONG_KPP - 1) / SPB_LONG_KPP;
+            if (out != nullptr) launch(build_sparse_kernel<N, PL, true, 2>, grid_long, maxd_long, 0, T.sparse_long_entries);
+            else launch(build_sparse_kernel<N, PL, false, 2>, grid_long, maxd_long, 0, T.sparse_long_entries);
+        });
     }
-#undef SPB_CASE
-#undef SPB_LAUNCH
-#undef SPB_ARGS
     HIP_TRY(hipGetLastError());
     return 0;
 }
@@ -410,7 +426,7 @@ extern "C" int mxm_build_em_matrix_sparse(const uint8_t *maj, const double *lhit
                                           const int64_t *order, int64_t R, int32_t H, int32_t S, double *M, int64_t ldm,
                                           int64_t *fallback, int64_t *n_fallback, void *stream) {
     MXM_ENTER();
-    if (M == nullptr) return fail(-1, "mxm_build_em_matrix_sparse: M required%s", "");
+    if (M == nullptr) return fail(-1, "mxm_build_em_matrix_sparse: M required");
     return build_sparse_impl("mxm_build_em_matrix_sparse", maj, lhit, lmiss, mk_ptr, mk_hap, mk_base, row_ptr, site, obs,
                              order, R, H, S, M, ldm, nullptr, fallback, n_fallback, (hipStream_t)stream);
 }
@@ -429,10 +445,10 @@ extern "C" int mxm_build_em_records(const uint8_t *maj, const double *lhit, cons
                                     int64_t *stats, int64_t *fallback, int64_t *n_fallback, void *stream) {
     MXM_ENTER();
     if (!mxm_linear_supported(H))
-        return fail(-1, "mxm_build_em_records: records need H in [65, 8192]%s (H=%lld)", "", H);
+        return fail(-1, "mxm_build_em_records: records need H in [65, 8192] (H=%d)", H);
     if (rec == nullptr || (reinterpret_cast<uintptr_t>(rec) & 15) || rec_bytes < (size_t)coded_ld(H) + 16 * ENC_MAX_CODES ||
         rec_off == nullptr || ndist == nullptr || rowmax == nullptr || stats == nullptr)
-        return fail(-1, "mxm_build_em_records: record buffer (16-byte aligned, >= one record) and output arrays required%s", "");
+        return fail(-1, "mxm_build_em_records: record buffer (16-byte aligned, >= one record) and output arrays required");
     spb_records out;
     out.rec = rec;
     out.rec_cap = (long long)rec_bytes;
@@ -451,14 +467,10 @@ static int linearize_wide(const double *M, int64_t ldm, int64_t R, int H, ST *P,
     const int nch = (H / 2 + 255) / 256;
     int cap = num_cu() * 2 < MXM_MAX_WG ? num_cu() * 2 : MXM_MAX_WG;
     const int nwg = clamp_grid((R + 1) / 2, cap);           // rows are dealt round-robin (row_deal)
-    switch (nch) {
-#define LW_CASE(n) case n: hipLaunchKernelGGL((linearize_wide_kernel<n, ST>), dim3(nwg), dim3(256), 0, s, M, ldm, R, H, P, ldp, rowmax); break;
-        LW_CASE(1) LW_CASE(2) LW_CASE(3) LW_CASE(4) LW_CASE(5) LW_CASE(6) LW_CASE(7) LW_CASE(8)
-        LW_CASE(9) LW_CASE(10) LW_CASE(11) LW_CASE(12) LW_CASE(13) LW_CASE(14) LW_CASE(15) LW_CASE(16)
-#undef LW_CASE
-        default: return 1;
-    }
-    return 0;
+    const bool ok = dispatch_width<16>(nch, [&](auto n) {
+        hipLaunchKernelGGL((linearize_wide_kernel<decltype(n)::value, ST>), dim3(nwg), dim3(256), 0, s, M, ldm, R, H, P, ldp, rowmax);
+    });
+    return ok ? 0 : 1;
 }
 
 static inline bool wide_rows_ok(const void *M, int64_t ldm, int H) {
@@ -467,8 +479,8 @@ static inline bool wide_rows_ok(const void *M, int64_t ldm, int H) {
 
 extern "C" int mxm_linearize(const double *M, int64_t ldm, int64_t R, int32_t H, double *P, int64_t ldp,
                              double *rowmax, void *stream) {
-    if (R < 0 || H <= 0) return fail(-1, "mxm_linearize: bad shape%s", "");
-    if (ldm < H || ldp < H || (ldp & 1)) return fail(-1, "mxm_linearize: ldp must be even and >= H%s (ldp=%lld)", "", ldp);
+    if (R < 0 || H <= 0) return fail(-1, "mxm_linearize: bad shape");
+    if (ldm < H || ldp < H || (ldp & 1)) return fail(-1, "mxm_linearize: ldp must be even and >= H (ldp=%lld)", (long long)ldp);
     if (R == 0) return 0;
     if (wide_rows_ok(M, ldm, H) && (reinterpret_cast<uintptr_t>(P) & 15) == 0 &&
         linearize_wide<double>(M, ldm, R, (int)H, P, ldp, rowmax, (hipStream_t)stream) == 0) {
@@ -488,7 +500,7 @@ extern "C" int mxm_set_timing_events(void *ev_start, void *ev_stop) {
 }
 
 extern "C" int mxm_set_min_rows_per_wg(int32_t n) {
-    if (n < 1) return fail(-1, "mxm_set_min_rows_per_wg: n < 1%s", "");
+    if (n < 1) return fail(-1, "mxm_set_min_rows_per_wg: n < 1");
     return tune_set([n](mxm_tuning &t) { t.min_rows_per_wg = n; });
 }
 
@@ -497,7 +509,7 @@ extern "C" int mxm_set_compact_restarts(int32_t mode) {
 }
 
 extern "C" int mxm_set_batch_tile(int32_t bt) {
-    if (bt < 1 || bt > 4) return fail(-1, "mxm_set_batch_tile: tile must be 1..4%s", "");
+    if (bt < 1 || bt > 4) return fail(-1, "mxm_set_batch_tile: tile must be 1..4");
     return tune_set([bt](mxm_tuning &t) { t.max_bt = bt; });
 }
 
@@ -512,11 +524,11 @@ extern "C" int mxm_set_sparse_long_entries(int32_t n) {
     return tune_set([n](mxm_tuning &t) { t.sparse_long_entries = n > 0 ? n : 0; });
 }
 extern "C" int mxm_set_coded_batch_tile(int32_t bt) {
-    if (bt != 1 && bt != 3) return fail(-1, "mxm_set_coded_batch_tile: 1 or 3, got %s%lld", "", bt);
+    if (bt != 1 && bt != 3) return fail(-1, "mxm_set_coded_batch_tile: 1 or 3, got %d", bt);
     return tune_set([bt](mxm_tuning &t) { t.coded_bt = bt; });
 }
 extern "C" int mxm_set_quad_encoder(int32_t kind) {
-    if (kind != 0 && kind != 1) return fail(-1, "mxm_set_quad_encoder: 0 or 1, got %s%lld", "", kind);
+    if (kind != 0 && kind != 1) return fail(-1, "mxm_set_quad_encoder: 0 or 1, got %d", kind);
     return tune_set([kind](mxm_tuning &t) { t.quad_encoder = kind; });
 }
 extern "C" int mxm_set_quad_left_grid(int32_t nwg) {
@@ -608,13 +620,10 @@ static int launch_wide(const double *P, int64_t ldp, const double *w, const doub
                        int H, int grid, double *partial, int64_t ldpart,
                        const mxm_em_state *state, mxm_slots slots, hipStream_t stream) {
     if constexpr (NCH * THREADS > MXM_MAX_COL2) {
-        return fail(-1, "mxm_em_iter: H=%s%lld outside the linear kernel's range", "", H);
+        return fail(-1, "mxm_em_iter: H=%d outside the linear kernel's range", H);
     } else {
         const size_t lds = (size_t)(BT - PREG) * NCH * THREADS * sizeof(d2);
-        if (lds > 60 * 1024 &&
-            raise_dynamic_lds(reinterpret_cast<const void *>(&em_iter_wide_kernel<THREADS, NCH, BT, NBUF, PREG>), lds,
-                              "em_iter_wide_kernel") != hipSuccess)
-            return -2;
+        RC_TRY(dynamic_lds_ok(reinterpret_cast<const void *>(&em_iter_wide_kernel<THREADS, NCH, BT, NBUF, PREG>), lds, "em_iter_wide_kernel"));
         hipLaunchKernelGGL((em_iter_wide_kernel<THREADS, NCH, BT, NBUF, PREG>), dim3(grid), dim3(THREADS), lds,
                            stream, P, ldp, w, props, R, H, partial, ldpart, state, slots);
         return 0;
@@ -625,14 +634,11 @@ template <int THREADS, int BT, int NBUF, int PREG>
 static int dispatch_wide(int nch, const double *P, int64_t ldp, const double *w, const double *props,
                          int64_t R, int H, int grid, double *partial,
                          int64_t ldpart, const mxm_em_state *state, mxm_slots slots, hipStream_t stream) {
-    switch (nch) {
-#define WIDE_CASE(n) case n: return launch_wide<THREADS, n, BT, NBUF, PREG>(P, ldp, w, props, R, H, grid, partial, ldpart, state, slots, stream);
-        WIDE_CASE(1) WIDE_CASE(2) WIDE_CASE(3) WIDE_CASE(4) WIDE_CASE(5) WIDE_CASE(6) WIDE_CASE(7) WIDE_CASE(8)
-        WIDE_CASE(9) WIDE_CASE(10) WIDE_CASE(11) WIDE_CASE(12) WIDE_CASE(13) WIDE_CASE(14) WIDE_CASE(15) WIDE_CASE(16)
-#undef WIDE_CASE
-        default: break;
-    }
-    return fail(-1, "mxm_em_iter: H=%s%lld outside the linear kernel's range", "", H);
+    int rc = 0;
+    const bool ok = dispatch_width<16>(nch, [&](auto n) {
+        rc = launch_wide<THREADS, decltype(n)::value, BT, NBUF, PREG>(P, ldp, w, props, R, H, grid, partial, ldpart, state, slots, stream);
+    });
+    return ok ? rc : fail(-1, "mxm_em_iter: H=%d outside the linear kernel's range", H);
 }
 
 static inline mxm_slots slots_from(int first) {
@@ -684,7 +690,7 @@ static int stream_linear_tile(const double *P, int64_t ldp, const double *w, con
 // The template instance stream_linear_tile launches for a tile of nb restarts at width H, as a profiler prints it
 // ("em_iter_wide_kernel<512, 6, 1, 3, 1>"): bench.py matches its committed counter files by this name.
 extern "C" int mxm_describe_stream_kernel(int32_t H, int32_t nb, char *buf, size_t len) {
-    if (buf == nullptr || len == 0 || H <= 0 || nb < 1 || nb > MXM_MAX_BT) return fail(-1, "mxm_describe_stream_kernel: bad arguments%s", "");
+    if (buf == nullptr || len == 0 || H <= 0 || nb < 1 || nb > MXM_MAX_BT) return fail(-1, "mxm_describe_stream_kernel: bad arguments");
     const int ncol2 = (H + 1) / 2;
     const bool alt = nb == 1;
     const int threads = alt ? MXM_V1B_THREADS : variant_threads(nb);
@@ -717,12 +723,19 @@ static int reduce_tile(const double *partial, int nwg, int nb, int H, double *co
     return 0;
 }
 
+// ... of ONE vector's partial rows (a restart on its own, a vote): no tile, no list check
+static int reduce_one(const double *partial, int nwg, int H, double *colsum, const mxm_em_state *state, hipStream_t stream) {
+    hipLaunchKernelGGL(colreduce_kernel, dim3((H + 63) / 64, 1), dim3(COLRED_THREADS), 0, stream, partial, part_ld(H), nwg, 1, H,
+                       (const double *)nullptr, colsum, const_cast<mxm_em_state *>(state), slots_from(0), wide_check{nullptr, 0, 0});
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
 static int em_iter_linear_tile(const double *P, int64_t ldp, const double *w, const double *props, int64_t R,
                                int H, int nb, mxm_slots slots, const mxm_em_state *state, double *colsum,
                                double *partial, hipStream_t stream, bool timed, const fin_args *fin = nullptr) {
     int nwg = 0;
-    const int rc = stream_linear_tile(P, ldp, w, props, R, H, nb, slots, state, partial, stream, timed, &nwg);
-    if (rc != 0) return rc;
+    RC_TRY(stream_linear_tile(P, ldp, w, props, R, H, nb, slots, state, partial, stream, timed, &nwg));
     return reduce_tile(partial, nwg, nb, H, colsum, state, slots, fin, stream);
 }
 
@@ -741,7 +754,7 @@ static int launch_wide_f32(const float *P, int64_t ldp, const double *w, const d
                            int grid, double *partial, int64_t ldpart,
                            const mxm_em_state *state, hipStream_t stream) {
     if constexpr (NCH * MXM_F32_THREADS > 2048) {
-        return fail(-1, "mxm_em_iter_f32: H=%s%lld outside the kernel's range", "", H);
+        return fail(-1, "mxm_em_iter_f32: H=%d outside the kernel's range", H);
     } else {
         hipLaunchKernelGGL((em_iter_wide_f32_kernel<MXM_F32_THREADS, NCH, MXM_F32_NBUF>), dim3(grid),
                            dim3(MXM_F32_THREADS), 0, stream, P, ldp, w, props, R, H, partial, ldpart,
@@ -760,18 +773,15 @@ static int em_iter_f32_one(const float *P, int64_t ldp, const double *w, const d
     if (cap > MXM_MAX_WG) cap = MXM_MAX_WG;
     const int nwg = clamp_grid((R + nbuf - 1) / nbuf, cap);
     if (timed && T.ev_start != nullptr) HIP_TRY(hipEventRecord(T.ev_start, stream));
-    switch (nch) {
-#define F32_CASE(n) case n: { const int lrc = launch_wide_f32<n>(P, ldp, w, props, R, H, nwg, partial, ldpart, state, stream); if (lrc != 0) return lrc; } break;
-        F32_CASE(1) F32_CASE(2) F32_CASE(3) F32_CASE(4) F32_CASE(5) F32_CASE(6) F32_CASE(7) F32_CASE(8)
-#undef F32_CASE
-        default: return fail(-1, "mxm_em_iter_f32: H=%s%lld outside the kernel's range", "", H);
-    }
+    int lrc = 0;
+    const bool ok = dispatch_width<8>(nch, [&](auto n) {
+        lrc = launch_wide_f32<decltype(n)::value>(P, ldp, w, props, R, H, nwg, partial, ldpart, state, stream);
+    });
+    if (!ok) return fail(-1, "mxm_em_iter_f32: H=%d outside the kernel's range", H);
+    if (lrc != 0) return lrc;
     HIP_TRY(hipGetLastError());
     if (timed && T.ev_stop != nullptr) HIP_TRY(hipEventRecord(T.ev_stop, stream));
-    hipLaunchKernelGGL(colreduce_kernel, dim3((H + 63) / 64, 1), dim3(COLRED_THREADS), 0, stream, partial, ldpart, nwg,
-                       1, H, (const double *)nullptr, colsum, const_cast<mxm_em_state *>(state), slots_from(0), wide_check{nullptr, 0, 0});
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return reduce_one(partial, nwg, H, colsum, state, stream);
 }
 
 // Narrow matrices (the refinement EM's contributor columns): one thread per row up to 32 columns,
@@ -800,8 +810,8 @@ static int launch_narrow(const double *M, int64_t ldm, const double *w, const do
 
 static int em_iter_log_one(const double *M, int64_t ldm, const double *w, const double *ln_props, int64_t R, int H,
                            const mxm_em_state *state, double *colsum, double *partial, hipStream_t stream) {
-    if (M == nullptr) return fail(-1, "mxm_em_iter: M is NULL and the linear path does not apply%s", "");
-    if (ln_props == nullptr) return fail(-1, "mxm_em_iter: ln_props is NULL and the log-space path needs it%s", "");
+    if (M == nullptr) return fail(-1, "mxm_em_iter: M is NULL and the linear path does not apply");
+    if (ln_props == nullptr) return fail(-1, "mxm_em_iter: ln_props is NULL and the log-space path needs it");
     const size_t lds = 2 * (size_t)H * sizeof(double);
     const int64_t ldpart = part_ld(H);
     int nwg;
@@ -817,26 +827,22 @@ static int em_iter_log_one(const double *M, int64_t ldm, const double *w, const 
         if (rc != 0) return rc;
     } else {
         nwg = clamp_grid(R, num_cu() * 2 < MXM_MAX_WG ? num_cu() * 2 : MXM_MAX_WG);
-        if (lds > 60 * 1024 && raise_dynamic_lds(reinterpret_cast<const void *>(&estep_log_kernel<true>), lds, "estep_log_kernel") != hipSuccess)
-            return -2;
+        RC_TRY(dynamic_lds_ok(reinterpret_cast<const void *>(&estep_log_kernel<true>), lds, "estep_log_kernel"));
         hipLaunchKernelGGL((estep_log_kernel<true>), dim3(nwg), dim3(ROW_THREADS), lds, stream, M, ldm, w, ln_props,
                            R, H, (double *)nullptr, (int64_t)0, 0, partial, ldpart, state);
         HIP_TRY(hipGetLastError());
     }
-    hipLaunchKernelGGL(colreduce_kernel, dim3((H + 63) / 64, 1), dim3(COLRED_THREADS), 0, stream, partial, ldpart, nwg, 1,
-                       H, (const double *)nullptr, colsum, const_cast<mxm_em_state *>(state), slots_from(0), wide_check{nullptr, 0, 0});
-    HIP_TRY(hipGetLastError());
-    return 0;
+    return reduce_one(partial, nwg, H, colsum, state, stream);
 }
 
 extern "C" int mxm_em_iter(const double *M, int64_t ldm, const double *P, int64_t ldp, const double *w,
                            const double *props, const double *ln_props, int64_t R, int32_t H, int32_t B,
                            const mxm_em_state *state, double *colsum, void *ws, size_t ws_bytes, void *stream) {
     MXM_ENTER();
-    if (R <= 0 || H <= 0 || B <= 0) return fail(-1, "mxm_em_iter: bad shape R=%s%lld H=%lld", "", R, H);
-    if (ws == nullptr || ws_bytes < mxm_workspace_bytes(R, H, B)) return fail(-1, "mxm_em_iter: workspace too small%s", "");
-    if (P != nullptr && ((ldp & 1) || ldp < H)) return fail(-1, "mxm_em_iter: ldp must be even and >= H%s", "");
-    if (M != nullptr && ldm < H) return fail(-1, "mxm_em_iter: ldm < H%s", "");
+    if (R <= 0 || H <= 0 || B <= 0) return fail(-1, "mxm_em_iter: bad shape R=%lld H=%d", (long long)R, H);
+    if (ws == nullptr || ws_bytes < mxm_workspace_bytes(R, H, B)) return fail(-1, "mxm_em_iter: workspace too small");
+    if (P != nullptr && ((ldp & 1) || ldp < H)) return fail(-1, "mxm_em_iter: ldp must be even and >= H");
+    if (M != nullptr && ldm < H) return fail(-1, "mxm_em_iter: ldm < H");
     const bool linear = (P != nullptr) && mxm_linear_supported(H);
     // restarts are taken in tiles of up to T.max_bt that share one pass over the matrix; the
     // scratch is reused tile after tile (same stream, so the passes are ordered)
@@ -866,8 +872,8 @@ extern "C" int mxm_em_iter(const double *M, int64_t ldm, const double *P, int64_
 
 extern "C" int mxm_linearize_f32(const double *M, int64_t ldm, int64_t R, int32_t H, float *P, int64_t ldp,
                                  double *rowmax, void *stream) {
-    if (R < 0 || H <= 0) return fail(-1, "mxm_linearize_f32: bad shape%s", "");
-    if (ldm < H || ldp < H || (ldp & 3)) return fail(-1, "mxm_linearize_f32: ldp must be a multiple of 4 and >= H%s (ldp=%lld)", "", ldp);
+    if (R < 0 || H <= 0) return fail(-1, "mxm_linearize_f32: bad shape");
+    if (ldm < H || ldp < H || (ldp & 3)) return fail(-1, "mxm_linearize_f32: ldp must be a multiple of 4 and >= H (ldp=%lld)", (long long)ldp);
     if (R == 0) return 0;
     if (wide_rows_ok(M, ldm, H) && (reinterpret_cast<uintptr_t>(P) & 7) == 0 && (ldp & 1) == 0 &&
         linearize_wide<float>(M, ldm, R, (int)H, P, ldp, rowmax, (hipStream_t)stream) == 0) {
@@ -885,10 +891,10 @@ extern "C" int mxm_em_iter_f32(const float *P, int64_t ldp, const double *w, con
                                int32_t H, int32_t B, const mxm_em_state *state, double *colsum, void *ws,
                                size_t ws_bytes, void *stream) {
     MXM_ENTER();
-    if (R <= 0 || H <= 0 || B <= 0) return fail(-1, "mxm_em_iter_f32: bad shape R=%s%lld H=%lld", "", R, H);
-    if (!mxm_linear_supported(H)) return fail(-1, "mxm_em_iter_f32: H=%s%lld outside the linear kernel's range", "", H);
-    if (P == nullptr || (ldp & 3) || ldp < H) return fail(-1, "mxm_em_iter_f32: ldp must be a multiple of 4 and >= H%s", "");
-    if (ws == nullptr || ws_bytes < mxm_workspace_bytes(R, H, B)) return fail(-1, "mxm_em_iter_f32: workspace too small%s", "");
+    if (R <= 0 || H <= 0 || B <= 0) return fail(-1, "mxm_em_iter_f32: bad shape R=%lld H=%d", (long long)R, H);
+    if (!mxm_linear_supported(H)) return fail(-1, "mxm_em_iter_f32: H=%d outside the linear kernel's range", H);
+    if (P == nullptr || (ldp & 3) || ldp < H) return fail(-1, "mxm_em_iter_f32: ldp must be a multiple of 4 and >= H");
+    if (ws == nullptr || ws_bytes < mxm_workspace_bytes(R, H, B)) return fail(-1, "mxm_em_iter_f32: workspace too small");
     for (int b = 0; b < B; ++b) {
         const int rc = em_iter_f32_one(P, ldp, w, props + (int64_t)b * H, R, (int)H, state ? state + b : nullptr,
                                        colsum + (int64_t)b * H, (double *)ws, (hipStream_t)stream, b == 0);
@@ -902,16 +908,16 @@ extern "C" size_t mxm_coded_bytes(int64_t R, int32_t H) { return mxm_record_byte
 
 extern "C" int mxm_encode_rows(const double *M, int64_t ldm, int64_t R, int32_t H, uint8_t *rec, size_t rec_bytes,
                                int64_t *rec_off, int32_t *ndist, double *rowmax, int64_t *stats, void *stream) {
-    if (R <= 0 || H <= 0 || ldm < H) return fail(-1, "mxm_encode_rows: bad shape R=%s%lld H=%lld", "", R, H);
+    if (R <= 0 || H <= 0 || ldm < H) return fail(-1, "mxm_encode_rows: bad shape R=%lld H=%d", (long long)R, H);
     // (round 5: any H in the linear kernels' range and any row stride -- a row's loads go through a descriptor of exactly
     // H doubles and need the doubles' own 8-byte alignment only; an odd H or an odd stride used to send the matrix back to
     // the 7 x larger dense form)
     if (!mxm_linear_supported(H) || (reinterpret_cast<uintptr_t>(M) & 7) != 0)
-        return fail(-1, "mxm_encode_rows: needs H in [65, 8192]%s (H=%lld ldm=%lld)", "", H, ldm);
+        return fail(-1, "mxm_encode_rows: needs H in [65, 8192] (H=%d ldm=%lld)", H, (long long)ldm);
     if (rec == nullptr || (reinterpret_cast<uintptr_t>(rec) & 15) || rec_bytes < (size_t)coded_ld(H) + 16 * ENC_MAX_CODES)
-        return fail(-1, "mxm_encode_rows: record buffer missing, unaligned or smaller than one record%s", "");
+        return fail(-1, "mxm_encode_rows: record buffer missing, unaligned or smaller than one record");
     if (rec_off == nullptr || ndist == nullptr || rowmax == nullptr || stats == nullptr)
-        return fail(-1, "mxm_encode_rows: output arrays required%s", "");
+        return fail(-1, "mxm_encode_rows: output arrays required");
     hipStream_t s = (hipStream_t)stream;
     HIP_TRY(hipMemsetAsync(stats, 0, 2 * sizeof(int64_t), s));
     const int ldc = coded_ld(H);
@@ -919,20 +925,22 @@ extern "C" int mxm_encode_rows(const double *M, int64_t ldm, int64_t R, int32_t 
     const int grid = clamp_grid(R, num_cu() * 4);
     // first pass: every row, byte codes; second pass: the rows it left without a record, 16-bit codes
     const int grid_w = clamp_grid((R + 31) / 32, num_cu() * 3);
-    switch (nch) {
-#define ENC_CASE(n) case n: hipLaunchKernelGGL((encode_rows_kernel<n>), dim3(grid), dim3(ENC_THREADS), 0, s, M, ldm, R, (int)H, ldc, rec, (int64_t)rec_bytes, rec_off, ndist, rowmax, reinterpret_cast<unsigned long long *>(stats)); \
-                    hipLaunchKernelGGL((encode_wide_rows_kernel<n>), dim3(grid_w), dim3(ENC_THREADS), 0, s, M, ldm, R, (int)H, ldc, rec, (int64_t)rec_bytes, rec_off, ndist, rowmax, reinterpret_cast<unsigned long long *>(stats)); break;
-        ENC_CASE(1) ENC_CASE(2) ENC_CASE(3) ENC_CASE(4) ENC_CASE(5) ENC_CASE(6) ENC_CASE(7) ENC_CASE(8)
-#undef ENC_CASE
-        default: return fail(-1, "mxm_encode_rows: H=%s%lld outside the kernel's range", "", H);
-    }
+    const bool ok = dispatch_width<8>(nch, [&](auto n) {
+        constexpr int NCH = decltype(n)::value;
+        unsigned long long *st = reinterpret_cast<unsigned long long *>(stats);
+        hipLaunchKernelGGL((encode_rows_kernel<NCH>), dim3(grid), dim3(ENC_THREADS), 0, s, M, ldm, R, (int)H, ldc, rec,
+                           (int64_t)rec_bytes, rec_off, ndist, rowmax, st);
+        hipLaunchKernelGGL((encode_wide_rows_kernel<NCH>), dim3(grid_w), dim3(ENC_THREADS), 0, s, M, ldm, R, (int)H, ldc, rec,
+                           (int64_t)rec_bytes, rec_off, ndist, rowmax, st);
+    });
+    if (!ok) return fail(-1, "mxm_encode_rows: H=%d outside the kernel's range", H);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 static int coded_check(const mxm_coded *c, int32_t H, const char *who) {
     if (c == nullptr || c->R <= 0 || H <= 0 || !mxm_linear_supported(H))
-        return fail(-1, "%s: bad coded matrix (rows %lld, H %lld)", who, c ? c->R : 0, H);
+        return fail(-1, "%s: bad coded matrix (rows %lld, H %d)", who, (long long)(c ? c->R : 0), H);
     if (c->rec == nullptr || c->rec_off == nullptr || c->ndist == nullptr) return fail(-1, "%s: coded matrix arrays missing", who);
     if (c->R_rest < 0 || (c->R_rest > 0 && (c->P_rest == nullptr || c->ldp_rest < H || (c->ldp_rest & 1) ||
                                             (reinterpret_cast<uintptr_t>(c->P_rest) & 15))))
@@ -944,8 +952,14 @@ static int coded_check(const mxm_coded *c, int32_t H, const char *who) {
             (reinterpret_cast<uintptr_t>(c->qrec) & 31))
             return fail(-1, "%s: quad dictionary arrays missing (or qrec not 32-byte aligned)", who);
         if (c->n_quad_rows + c->n_byte_rows + c->n_wide + c->R_rest != c->R)
-            return fail(-1, "%s: quad_rows + byte_rows + wide_rows + the dense rest must be all %lld rows", who, c->R);
+            return fail(-1, "%s: quad_rows + byte_rows + wide_rows + the dense rest must be all %lld rows", who, (long long)c->R);
     }
+    return 0;
+}
+
+static int rest_check(const char *who, int32_t H, const double *M_rest, int64_t ldm_rest, const int64_t *rest_rows, int64_t n_rest) {
+    if (n_rest < 0 || (n_rest > 0 && (M_rest == nullptr || rest_rows == nullptr || ldm_rest < H)))
+        return fail(-1, "%s: the rows without a record need M_rest, rest_rows and ldm_rest >= H", who);
     return 0;
 }
 
@@ -961,7 +975,7 @@ extern "C" size_t mxm_quad_bytes(int64_t R, int32_t H) {
 extern "C" int mxm_expand_tables(const uint8_t *maj, const int32_t *mk_ptr, const uint16_t *mk_hap, const uint8_t *mk_base,
                                  const uint8_t *map256, int32_t S, int32_t H, int64_t lde, uint8_t *out, void *stream) {
     if (maj == nullptr || mk_ptr == nullptr || mk_hap == nullptr || mk_base == nullptr || out == nullptr || S <= 0 || H <= 0 || lde < H)
-        return fail(-1, "mxm_expand_tables: bad arguments%s", "");
+        return fail(-1, "mxm_expand_tables: bad arguments");
     hipLaunchKernelGGL(expand_tables_kernel, dim3(clamp_grid(S, num_cu() * 8)), dim3(256), 0, (hipStream_t)stream, maj, mk_ptr, mk_hap,
                        mk_base, map256, (int)S, (int)H, lde, out);
     HIP_TRY(hipGetLastError());
@@ -976,10 +990,10 @@ extern "C" int mxm_quad_lists(const int32_t *ndist, const int32_t *nquad, int64_
                               int64_t *counts, void *scratch, size_t scratch_bytes, void *stream) {
     MXM_ENTER();
     if (ndist == nullptr || nquad == nullptr || R <= 0 || quad_rows == nullptr || byte_rows == nullptr || counts == nullptr)
-        return fail(-1, "mxm_quad_lists: bad arguments%s", "");
-    if (scratch == nullptr || scratch_bytes < mxm_quad_lists_scratch_bytes(R)) return fail(-1, "mxm_quad_lists: scratch too small%s", "");
+        return fail(-1, "mxm_quad_lists: bad arguments");
+    if (scratch == nullptr || scratch_bytes < mxm_quad_lists_scratch_bytes(R)) return fail(-1, "mxm_quad_lists: scratch too small");
     const int64_t nchunk = (R + QLIST_CHUNK - 1) / QLIST_CHUNK;
-    if (nchunk > 0x7fffffff) return fail(-1, "mxm_quad_lists: too many rows%s", "");
+    if (nchunk > 0x7fffffff) return fail(-1, "mxm_quad_lists: too many rows");
     hipStream_t s = (hipStream_t)stream;
     long long *cc = static_cast<long long *>(scratch);
     hipLaunchKernelGGL(quad_list_count_kernel, dim3((unsigned)nchunk), dim3(QLIST_THREADS), 0, s, ndist, nquad, R, cc);
@@ -993,12 +1007,12 @@ extern "C" int mxm_build_quads(const mxm_coded *c, int32_t H, uint8_t *qrec, siz
                                uint64_t *stats, void *stream) {
     MXM_ENTER();
     if (c == nullptr || c->R <= 0 || c->rec == nullptr || c->rec_off == nullptr || c->ndist == nullptr || !mxm_linear_supported(H))
-        return fail(-1, "mxm_build_quads: bad coded matrix (rows %s%lld, H %lld)", "", c ? c->R : 0, H);
+        return fail(-1, "mxm_build_quads: bad coded matrix (rows %lld, H %d)", (long long)(c ? c->R : 0), H);
     if (qoff == nullptr || nquad == nullptr || stats == nullptr || (qrec == nullptr && qrec_bytes > 0) ||
         (reinterpret_cast<uintptr_t>(qrec) & 31))
-        return fail(-1, "mxm_build_quads: qoff, nquad, stats and a 32-byte aligned qrec required%s", "");
+        return fail(-1, "mxm_build_quads: qoff, nquad, stats and a 32-byte aligned qrec required");
     const int ldc = coded_ld(H);
-    if (ldc / 4 > 8 * QUAD_THREADS) return fail(-1, "mxm_build_quads: H=%s%lld beyond eight quads per thread", "", H);
+    if (ldc / 4 > 8 * QUAD_THREADS) return fail(-1, "mxm_build_quads: H=%d beyond eight quads per thread", H);
     HIP_TRY(hipMemsetAsync(stats, 0, 2 * sizeof(uint64_t), (hipStream_t)stream));
     // (either way at most 5120 pieces of QUAD_CHUNK bytes are open at the end: what the caller's first guess leaves room for)
     if (T.quad_encoder == 1 && ldc / 4 <= 64 * QW_K)
@@ -1014,9 +1028,8 @@ extern "C" int mxm_build_quads(const mxm_coded *c, int32_t H, uint8_t *qrec, siz
 }
 
 extern "C" int mxm_decode_rows(const mxm_coded *c, int32_t H, double *P, int64_t ldp, void *stream) {
-    const int rc = coded_check(c, H, "mxm_decode_rows");
-    if (rc != 0) return rc;
-    if (P == nullptr || ldp < H) return fail(-1, "mxm_decode_rows: ldp < H%s", "");
+    RC_TRY(coded_check(c, H, "mxm_decode_rows"));
+    if (P == nullptr || ldp < H) return fail(-1, "mxm_decode_rows: ldp < H");
     hipLaunchKernelGGL(decode_rows_kernel, dim3(clamp_grid(c->R, num_cu() * 8)), dim3(256), 0, (hipStream_t)stream, c->rec,
                        c->rec_off, c->ndist, coded_ld(H), c->R, (int)H, P, ldp);
     HIP_TRY(hipGetLastError());
@@ -1027,35 +1040,34 @@ extern "C" int mxm_row_argmax_votes_coded(const mxm_coded *c, int32_t H, int32_t
                                           const double *props, const double *rowmax, const double *M_rest, int64_t ldm_rest,
                                           const int64_t *rest_rows, int64_t n_rest, const double *w, int32_t *best,
                                           double *votes, void *ws, size_t ws_bytes, void *stream) {
-    const int rc = coded_check(c, H, "mxm_row_argmax_votes_coded");
-    if (rc != 0) return rc;
+    RC_TRY(coded_check(c, H, "mxm_row_argmax_votes_coded"));
     if (ln_props == nullptr || best == nullptr || n_runs < 1 || n_runs > RECK_MAX_RUNS)
-        return fail(-1, "mxm_row_argmax_votes_coded: ln_props, best and 1..%s%lld runs required", "", (long long)RECK_MAX_RUNS);
+        return fail(-1, "mxm_row_argmax_votes_coded: ln_props, best and 1..%d runs required", RECK_MAX_RUNS);
     if (n_runs > 1 && (props == nullptr || rowmax == nullptr))
-        return fail(-1, "mxm_row_argmax_votes_coded: several runs need props and rowmax (each run's row normaliser)%s", "");
-    if (n_rest < 0 || (n_rest > 0 && (M_rest == nullptr || rest_rows == nullptr || ldm_rest < H)))
-        return fail(-1, "mxm_row_argmax_votes_coded: the rows without a record need M_rest, rest_rows and ldm_rest >= H%s", "");
+        return fail(-1, "mxm_row_argmax_votes_coded: several runs need props and rowmax (each run's row normaliser)");
+    RC_TRY(rest_check("mxm_row_argmax_votes_coded", H, M_rest, ldm_rest, rest_rows, n_rest));
     if (votes != nullptr && (ws == nullptr || ws_bytes < mxm_workspace_bytes(c->R, H, 1)))
-        return fail(-1, "mxm_row_argmax_votes_coded: workspace too small%s", "");
+        return fail(-1, "mxm_row_argmax_votes_coded: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     const size_t lse_lds = (size_t)n_runs * sizeof(double);
     const int ldc_a = coded_ld(H);
     const int nch_a = (ldc_a / 4 + 255) / 256;
-    bool fast = n_runs == 1 && nch_a <= 8;
-    if (fast) {
-        // one run: the normaliser drops out -- the register-resident form (records_argmax_kernel)
-        switch (nch_a) {
-            // one wave of workgroups: as many as are resident at once (a second, partial wave of equally long workgroups
-            // would double the kernel's time)
-#define RA_CASE(n) case n: { int per_cu = 2; if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, records_argmax_narrow_kernel<n>, 256, 0) != hipSuccess || per_cu < 1) { (void)hipGetLastError(); per_cu = 2; } \
-                hipLaunchKernelGGL((records_argmax_narrow_kernel<n>), dim3(clamp_grid(c->R, num_cu() * per_cu)), dim3(256), 0, s, c->rec, c->rec_off, c->ndist, ldc_a, c->R, (int)H, ln_props, best); \
-                /* the wide rows, found from ndist itself (no list: the vote must not depend on one) */ \
-                hipLaunchKernelGGL((records_argmax_kernel<n, true>), dim3(clamp_grid((c->R + 255) / 256, num_cu() * 2)), dim3(256), 0, s, c->rec, c->rec_off, c->ndist, ldc_a, c->R, (int)H, ln_props, best, (const int64_t *)nullptr); } break;
-            RA_CASE(1) RA_CASE(2) RA_CASE(3) RA_CASE(4) RA_CASE(5) RA_CASE(6) RA_CASE(7) RA_CASE(8)
-#undef RA_CASE
-            default: fast = false;
+    // one run: the normaliser drops out -- the register-resident form (records_argmax_kernel)
+    const bool fast = n_runs == 1 && dispatch_width<8>(nch_a, [&](auto n) {
+        constexpr int NCH = decltype(n)::value;
+        // one wave of workgroups: as many as are resident at once (a second, partial wave of equally long workgroups
+        // would double the kernel's time)
+        int per_cu = 2;
+        if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, records_argmax_narrow_kernel<NCH>, 256, 0) != hipSuccess || per_cu < 1) {
+            (void)hipGetLastError();
+            per_cu = 2;
         }
-    }
+        hipLaunchKernelGGL((records_argmax_narrow_kernel<NCH>), dim3(clamp_grid(c->R, num_cu() * per_cu)), dim3(256), 0, s, c->rec,
+                           c->rec_off, c->ndist, ldc_a, c->R, (int)H, ln_props, best);
+        // the wide rows, found from ndist itself (no list: the vote must not depend on one)
+        hipLaunchKernelGGL((records_argmax_kernel<NCH, true>), dim3(clamp_grid((c->R + 255) / 256, num_cu() * 2)), dim3(256), 0, s,
+                           c->rec, c->rec_off, c->ndist, ldc_a, c->R, (int)H, ln_props, best, (const int64_t *)nullptr);
+    });
     if (!fast)
         hipLaunchKernelGGL(posterior_argmax_kernel<true>, dim3(clamp_grid(c->R, num_cu() * 8)), dim3(256), lse_lds, s, c->rec, c->rec_off,
                            c->ndist, coded_ld(H), (const double *)nullptr, (int64_t)0, (const int64_t *)nullptr, c->R, (int)H,
@@ -1071,32 +1083,22 @@ extern "C" int mxm_row_argmax_votes_coded(const mxm_coded *c, int32_t H, int32_t
         const int64_t ldpart = part_ld(H);
         const int nwg = clamp_grid((c->R + 255) / 256, num_cu() * 2 < MXM_MAX_WG ? num_cu() * 2 : MXM_MAX_WG);
         const size_t vlds = (size_t)H * sizeof(double);
-        if (vlds > 150 * 1024) return fail(-1, "mxm_row_argmax_votes_coded: H=%s%lld too wide for the vote kernel", "", H);
-        if (vlds > 60 * 1024 && raise_dynamic_lds(reinterpret_cast<const void *>(&votes_from_best_kernel), vlds, "votes_from_best_kernel") != hipSuccess)
-            return -2;
+        RC_TRY(dynamic_lds_ok(reinterpret_cast<const void *>(&votes_from_best_kernel), vlds, "votes_from_best_kernel",
+                              "mxm_row_argmax_votes_coded", H, "too wide for the vote kernel"));
         hipLaunchKernelGGL(votes_from_best_kernel, dim3(nwg), dim3(256), vlds, s, best, w, c->R, (int)H, (double *)ws, ldpart);
         HIP_TRY(hipGetLastError());
-        hipLaunchKernelGGL(colreduce_kernel, dim3((H + 63) / 64, 1), dim3(COLRED_THREADS), 0, s, (const double *)ws, ldpart, nwg,
-                           1, (int)H, (const double *)nullptr, votes, (mxm_em_state *)nullptr, slots_from(0), wide_check{nullptr, 0, 0});
-        HIP_TRY(hipGetLastError());
+        return reduce_one((const double *)ws, nwg, (int)H, votes, nullptr, s);
     }
-    return 0;
-}
-
-static int rest_check(const char *who, int32_t H, const double *M_rest, int64_t ldm_rest, const int64_t *rest_rows, int64_t n_rest) {
-    if (n_rest < 0 || (n_rest > 0 && (M_rest == nullptr || rest_rows == nullptr || ldm_rest < H)))
-        return fail(-1, "%s: the rows without a record need M_rest, rest_rows and ldm_rest >= H", who);
     return 0;
 }
 
 extern "C" int mxm_em_step_coded(const mxm_coded *c, int32_t H, const double *ln_props, const double *props,
                                  const double *rowmax, const double *M_rest, int64_t ldm_rest, const int64_t *rest_rows,
                                  int64_t n_rest, double *out, int64_t ldo, int32_t mode, void *stream) {
-    int rc = coded_check(c, H, "mxm_em_step_coded");
-    if (rc != 0) return rc;
+    RC_TRY(coded_check(c, H, "mxm_em_step_coded"));
     if (ln_props == nullptr || props == nullptr || rowmax == nullptr || out == nullptr || ldo < H)
-        return fail(-1, "mxm_em_step_coded: bad arguments%s", "");
-    if ((rc = rest_check("mxm_em_step_coded", H, M_rest, ldm_rest, rest_rows, n_rest)) != 0) return rc;
+        return fail(-1, "mxm_em_step_coded: bad arguments");
+    RC_TRY(rest_check("mxm_em_step_coded", H, M_rest, ldm_rest, rest_rows, n_rest));
     hipLaunchKernelGGL(coded_posterior_kernel, dim3(clamp_grid(c->R, num_cu() * 8)), dim3(256), 0, (hipStream_t)stream, c->rec,
                        c->rec_off, c->ndist, coded_ld(H), c->R, (int)H, ln_props, props, rowmax, out, ldo, (int)mode);
     HIP_TRY(hipGetLastError());
@@ -1104,9 +1106,8 @@ extern "C" int mxm_em_step_coded(const mxm_coded *c, int32_t H, const double *ln
         // the rows without a record: the reference's E-step in log space on their dense copies, each written to its
         // own row of `out`
         const size_t lds = 2 * (size_t)H * sizeof(double);
-        if (lds > 150 * 1024) return fail(-1, "mxm_em_step_coded: H=%s%lld too large", "", H);
-        if (lds > 60 * 1024 && raise_dynamic_lds(reinterpret_cast<const void *>(&estep_log_kernel<false>), lds, "estep_log_kernel") != hipSuccess)
-            return -2;
+        RC_TRY(dynamic_lds_ok(reinterpret_cast<const void *>(&estep_log_kernel<false>), lds, "estep_log_kernel", "mxm_em_step_coded", H,
+                              "too large"));
         hipLaunchKernelGGL((estep_log_kernel<false>), dim3(clamp_grid(n_rest, num_cu() * 2)), dim3(ROW_THREADS), lds,
                            (hipStream_t)stream, M_rest, ldm_rest, (const double *)nullptr, ln_props, n_rest, (int)H, out, ldo,
                            (int)mode, (double *)nullptr, (int64_t)0, (const mxm_em_state *)nullptr, rest_rows);
@@ -1118,10 +1119,9 @@ extern "C" int mxm_em_step_coded(const mxm_coded *c, int32_t H, const double *ln
 extern "C" int mxm_gather_columns_coded(const mxm_coded *c, int32_t H, const int32_t *cols, int32_t nC, const double *M_rest,
                                         int64_t ldm_rest, const int64_t *rest_rows, int64_t n_rest, double *out,
                                         int64_t ldo, void *stream) {
-    int rc = coded_check(c, H, "mxm_gather_columns_coded");
-    if (rc != 0) return rc;
-    if (cols == nullptr || out == nullptr || nC <= 0 || ldo < nC) return fail(-1, "mxm_gather_columns_coded: bad arguments%s", "");
-    if ((rc = rest_check("mxm_gather_columns_coded", H, M_rest, ldm_rest, rest_rows, n_rest)) != 0) return rc;
+    RC_TRY(coded_check(c, H, "mxm_gather_columns_coded"));
+    if (cols == nullptr || out == nullptr || nC <= 0 || ldo < nC) return fail(-1, "mxm_gather_columns_coded: bad arguments");
+    RC_TRY(rest_check("mxm_gather_columns_coded", H, M_rest, ldm_rest, rest_rows, n_rest));
     const int64_t blocks = (c->R * nC + 255) / 256;
     hipLaunchKernelGGL(coded_gather_columns_kernel, dim3(clamp_grid(blocks, num_cu() * 16)), dim3(256), 0, (hipStream_t)stream,
                        c->rec, c->rec_off, c->ndist, coded_ld(H), c->R, cols, (int)nC, out, ldo);
@@ -1143,13 +1143,17 @@ template <int THREADS, int NBUF, int MINWG>
 static int launch_coded(int nch, int nwg, hipStream_t stream, const mxm_coded *c, int ldc, const double *w, const double *props,
                         int H, double *partial, int64_t ldpart, const mxm_em_state *state, int run,
                         const int64_t *row_list = nullptr, int64_t n_list = 0, int part_row0 = 0) {
-    switch (nch) {
-#define COD_CASE(n) case n: if constexpr (n * THREADS <= 2048) { hipLaunchKernelGGL((em_iter_coded_kernel<THREADS, n, NBUF, MINWG>), dim3(nwg), dim3(THREADS), 0, stream, c->rec, c->rec_off, c->ndist, ldc, w, c->wide_rows, c->n_wide, props, c->R, H, partial, ldpart, state, run, row_list, n_list, c->nquad, part_row0); return 0; } break;
-        COD_CASE(1) COD_CASE(2) COD_CASE(3) COD_CASE(4) COD_CASE(5) COD_CASE(6) COD_CASE(7) COD_CASE(8)
-#undef COD_CASE
-        default: break;
-    }
-    return fail(-1, "mxm_em_iter_coded: H=%s%lld outside the kernel's range", "", H);
+    bool launched = false;
+    (void)dispatch_width<8>(nch, [&](auto n) {
+        constexpr int NCH = decltype(n)::value;
+        if constexpr (NCH * THREADS <= 2048) {
+            hipLaunchKernelGGL((em_iter_coded_kernel<THREADS, NCH, NBUF, MINWG>), dim3(nwg), dim3(THREADS), 0, stream, c->rec, c->rec_off,
+                               c->ndist, ldc, w, c->wide_rows, c->n_wide, props, c->R, H, partial, ldpart, state, run, row_list, n_list,
+                               c->nquad, part_row0);
+            launched = true;
+        }
+    });
+    return launched ? 0 : fail(-1, "mxm_em_iter_coded: H=%d outside the kernel's range", H);
 }
 #define QUAD_MAX_NCH 6              // H <= 6144: the instances of the quad pass that compile without scratch
 // The leftover pass's share of a grid of `slots` workgroups it shares with the quad pass, by the measured cost of a row in
@@ -1170,23 +1174,22 @@ static int quad_left_share(const mxm_coded *c, int slots) {
 }
 static int launch_quad(int nch, int nwg, hipStream_t stream, const mxm_coded *c, const double *w, const double *props, int H,
                        double *partial, int64_t ldpart, const mxm_em_state *state, int run) {
-    switch (nch) {
-#define QUAD_CASE(n) case n: hipLaunchKernelGGL((em_iter_quad_kernel<n, 4>), dim3(nwg), dim3(QUAD_THREADS), 0, stream, c->qrec, c->qoff, c->nquad, c->quad_rows, c->n_quad_rows, c->R, w, props, H, partial, ldpart, 0, state, run); return 0;
-        QUAD_CASE(1) QUAD_CASE(2) QUAD_CASE(3) QUAD_CASE(4) QUAD_CASE(5) QUAD_CASE(6)      // (7, 8: 35 registers spilled)
-#undef QUAD_CASE
-        default: break;
-    }
-    return fail(-1, "mxm_em_iter_coded: H=%s%lld outside the quad kernel's range", "", H);
+    const bool ok = dispatch_width<QUAD_MAX_NCH>(nch, [&](auto n) {               // (7, 8: 35 registers spilled)
+        hipLaunchKernelGGL((em_iter_quad_kernel<decltype(n)::value, 4>), dim3(nwg), dim3(QUAD_THREADS), 0, stream, c->qrec, c->qoff,
+                           c->nquad, c->quad_rows, c->n_quad_rows, c->R, w, props, H, partial, ldpart, 0, state, run);
+    });
+    return ok ? 0 : fail(-1, "mxm_em_iter_coded: H=%d outside the quad kernel's range", H);
 }
 static int launch_quad_coded(int nch, int nwg, int nwg_left, hipStream_t stream, const mxm_coded *c, int ldc, const double *w,
                              const double *props, int H, double *partial, int64_t ldpart, const mxm_em_state *state, int run) {
-    switch (nch) {
-#define QC_CASE(n) case n: hipLaunchKernelGGL((em_iter_quad_coded_kernel<n, 4>), dim3(nwg), dim3(QUAD_THREADS), 0, stream, c->rec, c->rec_off, c->ndist, ldc, c->wide_rows, c->n_wide, c->byte_rows != nullptr ? c->byte_rows : c->quad_rows /* an EMPTY list is still a list: a null pointer would mean "every row" to the pass */, c->n_byte_rows, c->qrec, c->qoff, c->nquad, c->quad_rows, c->n_quad_rows, c->R, w, props, H, partial, ldpart, nwg_left, state, run); return 0;
-        QC_CASE(1) QC_CASE(2) QC_CASE(3) QC_CASE(4) QC_CASE(5) QC_CASE(6)
-#undef QC_CASE
-        default: break;
-    }
-    return fail(-1, "mxm_em_iter_coded: H=%s%lld outside the quad kernel's range", "", H);
+    // an EMPTY list is still a list: a null pointer would mean "every row" to the pass
+    const int64_t *byte_rows = c->byte_rows != nullptr ? c->byte_rows : c->quad_rows;
+    const bool ok = dispatch_width<QUAD_MAX_NCH>(nch, [&](auto n) {
+        hipLaunchKernelGGL((em_iter_quad_coded_kernel<decltype(n)::value, 4>), dim3(nwg), dim3(QUAD_THREADS), 0, stream, c->rec,
+                           c->rec_off, c->ndist, ldc, c->wide_rows, c->n_wide, byte_rows, c->n_byte_rows, c->qrec, c->qoff, c->nquad,
+                           c->quad_rows, c->n_quad_rows, c->R, w, props, H, partial, ldpart, nwg_left, state, run);
+    });
+    return ok ? 0 : fail(-1, "mxm_em_iter_coded: H=%d outside the quad kernel's range", H);
 }
 
 // One restart's pass over a coded matrix: dictionary rows through em_iter_coded_kernel, the dense rest
@@ -1273,14 +1276,17 @@ static int em_iter_coded_batched(const mxm_coded *c, const double *w, const doub
     // two launches on the same grid: the quad rows start the partial sums, the leftover rows (byte-coded without quads,
     // wide) are added to them (quad_batched_kernels.hpp: as one kernel the three row loops spill into the quad rows' loop)
     const bool left = c->n_byte_rows > 0 || c->n_wide > 0;
-    switch (nch) {
-#define QB_ARGS c->rec, c->rec_off, c->ndist, ldc, wide_rows, c->n_wide, byte_rows, c->n_byte_rows, c->qrec, c->qoff, c->nquad, c->quad_rows, c->n_quad_rows, c->R, w, props, H, partial, ldpart, state, sl
-#define QB_CASE(n) case n: hipLaunchKernelGGL((em_iter_quad_batched_kernel<QB_BT, n, 1>), dim3(nwg), dim3(QB_THREADS), 0, stream, QB_ARGS); if (left) hipLaunchKernelGGL((em_iter_quad_batched_kernel<QB_BT, n, 6>), dim3(nwg), dim3(QB_THREADS), 0, stream, QB_ARGS); break;
-        QB_CASE(1) QB_CASE(2) QB_CASE(3)
-#undef QB_CASE
-#undef QB_ARGS
-        default: return fail(-1, "mxm_em_iter_coded: H=%s%lld outside the batched quad kernel's range", "", H);
-    }
+    const bool ok = dispatch_width<3>(nch, [&](auto n) {
+        constexpr int NCH = decltype(n)::value;
+        auto pass = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(nwg), dim3(QB_THREADS), 0, stream, c->rec, c->rec_off, c->ndist, ldc, wide_rows, c->n_wide,
+                               byte_rows, c->n_byte_rows, c->qrec, c->qoff, c->nquad, c->quad_rows, c->n_quad_rows, c->R, w, props, H,
+                               partial, ldpart, state, sl);
+        };
+        pass(em_iter_quad_batched_kernel<QB_BT, NCH, 1>);
+        if (left) pass(em_iter_quad_batched_kernel<QB_BT, NCH, 6>);
+    });
+    if (!ok) return fail(-1, "mxm_em_iter_coded: H=%d outside the batched quad kernel's range", H);
     HIP_TRY(hipGetLastError());
     if (timed && T.ev_stop != nullptr) HIP_TRY(hipEventRecord(T.ev_stop, stream));
     int nwg_rest = 0;
@@ -1297,21 +1303,18 @@ static int em_iter_coded_batched(const mxm_coded *c, const double *w, const doub
 extern "C" int mxm_em_iter_coded(const mxm_coded *c, const double *w, const double *props, int32_t H, int32_t B,
                                  mxm_em_state *state, double *colsum, void *ws, size_t ws_bytes, void *stream) {
     MXM_ENTER();
-    const int rc = coded_check(c, H, "mxm_em_iter_coded");
-    if (rc != 0) return rc;
-    if (B <= 0 || props == nullptr || colsum == nullptr) return fail(-1, "mxm_em_iter_coded: bad arguments%s", "");
-    if (ws == nullptr || ws_bytes < mxm_workspace_bytes(c->R, H, B)) return fail(-1, "mxm_em_iter_coded: workspace too small%s", "");
+    RC_TRY(coded_check(c, H, "mxm_em_iter_coded"));
+    if (B <= 0 || props == nullptr || colsum == nullptr) return fail(-1, "mxm_em_iter_coded: bad arguments");
+    if (ws == nullptr || ws_bytes < mxm_workspace_bytes(c->R, H, B)) return fail(-1, "mxm_em_iter_coded: workspace too small");
     // beside a quad dictionary full tiles of QB_BT restarts share a pass (the remainder: one per pass)
     int b = 0;
     if (coded_batch_ok(c, (int)H)) {
         for (; b + QB_BT <= B; b += QB_BT) {
-            const int irc = em_iter_coded_batched(c, w, props, (int)H, slots_from(b), state, colsum, (double *)ws, (hipStream_t)stream, b == 0);
-            if (irc != 0) return irc;
+            RC_TRY(em_iter_coded_batched(c, w, props, (int)H, slots_from(b), state, colsum, (double *)ws, (hipStream_t)stream, b == 0));
         }
     }
     for (; b < B; ++b) {
-        const int irc = em_iter_coded_one(c, w, props, (int)H, b, state, colsum, (double *)ws, (hipStream_t)stream, b == 0);
-        if (irc != 0) return irc;
+        RC_TRY(em_iter_coded_one(c, w, props, (int)H, b, state, colsum, (double *)ws, (hipStream_t)stream, b == 0));
     }
     return 0;
 }
@@ -1331,7 +1334,7 @@ extern "C" int mxm_restart_tile(int32_t H) {
 
 extern "C" int mxm_m_finalize(const double *colsum, double *ln_cur, double *ln_new, double *props_cur, int32_t H,
                               int32_t B, double tol, int32_t max_iter, mxm_em_state *state, void *stream) {
-    if (H <= 0 || B <= 0 || state == nullptr) return fail(-1, "mxm_m_finalize: bad arguments%s", "");
+    if (H <= 0 || B <= 0 || state == nullptr) return fail(-1, "mxm_m_finalize: bad arguments");
     if (H > 64 * FIN_MAX_BLOCKS) {                        // any width: one workgroup per restart
         hipLaunchKernelGGL(finalize_any_kernel, dim3(1, B), dim3(FIN_THREADS), 0, (hipStream_t)stream, colsum, ln_cur, ln_new,
                            props_cur, (int)H, tol, (int)max_iter, state, 0, 0, slots_from(0));
@@ -1448,7 +1451,7 @@ static bool fused_coded_eligible(const mxm_coded *c, int H, int B, size_t ws_byt
 // Diagnostic (-DFUSED_STAMPS builds): the per-phase clock sums of the last one-launch loop, from the
 // sync block at the start of `ws`; all zeros in the shipped library.
 extern "C" int mxm_diag_fused_stamps(const void *ws, unsigned long long *out_host) {
-    if (ws == nullptr || out_host == nullptr) return fail(-1, "mxm_diag_fused_stamps: bad arguments%s", "");
+    if (ws == nullptr || out_host == nullptr) return fail(-1, "mxm_diag_fused_stamps: bad arguments");
     const fused_sync *sync = reinterpret_cast<const fused_sync *>(ws);
     HIP_TRY(hipMemcpy(out_host, sync->stamps, sizeof(sync->stamps), hipMemcpyDeviceToHost));
     return 0;
@@ -1542,14 +1545,38 @@ static bool launch_fused_narrow_one(int nwg, hipStream_t s, const double *M, int
 static bool launch_fused_narrow(int nwg, int rpt, hipStream_t s, const double *M, int64_t ldm, const double *w, int64_t R, int H,
                                 int B, double *ln_cur, double *ln_new, double *props_cur, mxm_em_state *state, double tol,
                                 int max_iter, int chunk, double *partial, fused_sync *sync) {
-#define FN_ARGS nwg, s, M, ldm, w, R, H, B, ln_cur, ln_new, props_cur, state, tol, max_iter, chunk, partial, sync
-#define FN_RPT(hm) (rpt == 1 ? launch_fused_narrow_one<hm, 1>(FN_ARGS) : rpt == 2 ? launch_fused_narrow_one<hm, 2>(FN_ARGS) \
-                   : rpt == 4 ? launch_fused_narrow_one<hm, 4>(FN_ARGS) : rpt == 8 ? launch_fused_narrow_one<hm, 8>(FN_ARGS) : false)
-    if (H <= 4) return FN_RPT(4);
-    if (H <= 8) return FN_RPT(8);
-    return FN_RPT(16);
-#undef FN_RPT
-#undef FN_ARGS
+    bool fits = false;
+    auto columns = [&](auto hmax) {                      // rows per thread: 1, 2, 4 or 8
+        (void)dispatch_width<8>(rpt, [&](auto k) {
+            constexpr int HMAX = decltype(hmax)::value, RPT = decltype(k)::value;
+            if constexpr ((RPT & (RPT - 1)) == 0)
+                fits = launch_fused_narrow_one<HMAX, RPT>(nwg, s, M, ldm, w, R, H, B, ln_cur, ln_new, props_cur, state, tol, max_iter,
+                                                          chunk, partial, sync);
+        });
+    };
+    if (H <= 4) columns(std::integral_constant<int, 4>{});
+    else if (H <= 8) columns(std::integral_constant<int, 8>{});
+    else columns(std::integral_constant<int, 16>{});
+    return fits;
+}
+
+// The form of the one-launch loop and the matrix it reads: records (`coded`), a narrow log-space matrix (M, ldm) or the
+// linear matrix (P, ldp; rows or columns split over the workgroups, decided per launch).
+enum class fused_route { none, records, narrow, dense };
+struct fused_matrix {
+    fused_route route;
+    const mxm_coded *coded;
+    const double *M;
+    int64_t ldm;
+    const double *P;
+    int64_t ldp;
+};
+
+// the states of n restarts (samples), once the stream has got there
+static int read_state(mxm_em_state *state_host, const mxm_em_state *state, int n, hipStream_t s) {
+    HIP_TRY(hipMemcpyAsync(state_host, state, sizeof(mxm_em_state) * n, hipMemcpyDeviceToHost, s));
+    HIP_TRY(hipStreamSynchronize(s));
+    return 0;
 }
 
 // The loop of every restart in [0, B) that is not done yet, in launches of at most `chunk` iterations
@@ -1559,11 +1586,12 @@ static bool launch_fused_narrow(int nwg, int rpt, hipStream_t s, const double *M
 // process or stream holding CUs): the loop vectors and states are then back at their values from before that launch
 // (snapshot at the tail of the workspace), so the caller can continue with the per-iteration kernels.
 #define MXM_FUSED_GAVE_UP 1
-static int em_loop_fused(const double *P, int64_t ldp, const double *w, int64_t R, int32_t H, int32_t B,
-                         double *props_cur, double *ln_cur, double *ln_new, mxm_em_state *state, double tol,
-                         int32_t max_iter, int32_t chunk, void *ws, size_t ws_bytes, hipStream_t s,
-                         mxm_em_state *state_host, const mxm_coded *coded = nullptr, const double *M_narrow = nullptr,
-                         int64_t ldm_narrow = 0) {
+static int em_loop_fused(const fused_matrix &m, const double *w, int64_t R, int32_t H, int32_t B, double *props_cur,
+                         double *ln_cur, double *ln_new, mxm_em_state *state, double tol, int32_t max_iter, int32_t chunk,
+                         void *ws, size_t ws_bytes, hipStream_t s, mxm_em_state *state_host) {
+    const mxm_coded *coded = m.coded;
+    const double *P = m.P;
+    const int64_t ldp = m.ldp;
     // The persistent grid needs every workgroup resident, one per CU.  Two such grids in flight on one
     // device (two host threads, two streams) can each hold a part of the CUs and wait for the rest for
     // ever -- the bounded spins would end both after seconds.  Inside one process the launches are
@@ -1571,9 +1599,9 @@ static int em_loop_fused(const double *P, int64_t ldp, const double *w, int64_t 
     static std::mutex one_loop_at_a_time;
     std::lock_guard<std::mutex> guard(one_loop_at_a_time);
     int narrow_rpt = 1;
-    const int nwg = M_narrow != nullptr ? fused_narrow_grid(R, (int)H, &narrow_rpt)
-                    : coded != nullptr  ? fused_coded_grid(coded->R)
-                                        : (num_cu() < MXM_MAX_WG ? num_cu() : MXM_MAX_WG);
+    const int nwg = m.route == fused_route::narrow    ? fused_narrow_grid(R, (int)H, &narrow_rpt)
+                    : m.route == fused_route::records ? fused_coded_grid(coded->R)
+                                                      : (num_cu() < MXM_MAX_WG ? num_cu() : MXM_MAX_WG);
     const int64_t ldpart = part_ld(H);
     char *base = static_cast<char *>(ws);
     fused_sync *sync = reinterpret_cast<fused_sync *>(base);
@@ -1595,8 +1623,7 @@ static int em_loop_fused(const double *P, int64_t ldp, const double *w, int64_t 
     if (chunk < 1) chunk = 1;
     bool launched_once = false;
     for (;;) {
-        HIP_TRY(hipMemcpyAsync(state_host, state, sizeof(mxm_em_state) * B, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        RC_TRY(read_state(state_host, state, B, s));
         bool all_done = true, gave_up = false;
         for (int b = 0; b < B; ++b) {
             gave_up = gave_up || state_host[b].done < 0;
@@ -1605,10 +1632,9 @@ static int em_loop_fused(const double *P, int64_t ldp, const double *w, int64_t 
         if (gave_up) {
             // the grid barrier timed out: undo the launch (its vectors are mid-iteration) and hand back
             HIP_TRY(snapshot(false));
-            HIP_TRY(hipMemcpyAsync(state_host, state, sizeof(mxm_em_state) * B, hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            fail(-3, "mxm_em_loop: the one-launch loop's grid barrier timed out: not all %s%lld workgroups became resident "
-                     "(is another process or stream using the GPU?)", "", nwg);
+            RC_TRY(read_state(state_host, state, B, s));
+            fail(-3, "mxm_em_loop: the one-launch loop's grid barrier timed out: not all %d workgroups became resident "
+                     "(is another process or stream using the GPU?)", nwg);
             return MXM_FUSED_GAVE_UP;
         }
         if (launched_once && T.progress != nullptr) T.progress(state_host, B, T.progress_user);
@@ -1618,22 +1644,21 @@ static int em_loop_fused(const double *P, int64_t ldp, const double *w, int64_t 
         if (T.fused_force_abort)                                       // test hook: as if a workgroup had given up
             HIP_TRY(hipMemsetAsync(&sync->abort_[0], 1, sizeof(unsigned), s));
         bool fits = true;
-        if (M_narrow != nullptr) {
+        if (m.route == fused_route::narrow) {
             // narrow matrix: [sync][partial sums 2 x H x grid]; the rows live in registers for the whole launch
-            fits = launch_fused_narrow(nwg, narrow_rpt, s, M_narrow, ldm_narrow, w, R, (int)H, (int)B, ln_cur, ln_new, props_cur,
+            fits = launch_fused_narrow(nwg, narrow_rpt, s, m.M, m.ldm, w, R, (int)H, (int)B, ln_cur, ln_new, props_cur,
                                        state, tol, (int)max_iter, (int)chunk, reinterpret_cast<double *>(base + fused_sync_bytes()), sync);
-        } else if (coded != nullptr) {
+        } else if (m.route == fused_route::records) {
             // records: [sync][T (1 row)][partial rows]; the metadata of a workgroup's rows stays in LDS for the whole
             // launch when they fit its blocks (256 rows and 256 wide rows per workgroup)
             const int ldc = coded_ld(H);
             const int cnch = (ldc / 4 + FCODED_THREADS - 1) / FCODED_THREADS;
             const bool resident = (coded->R + nwg - 1) / nwg <= FCODED_THREADS && (coded->n_wide + nwg - 1) / nwg <= FCODED_THREADS;
-            switch (cnch) {
-#define FC_CASE(n) case n: fits = launch_fused_coded<n>(nwg, resident, s, coded, ldc, w, (int)H, (int)B, ln_cur, ln_new, props_cur, state, tol, (int)max_iter, (int)chunk, partial, ldpart, tbuf, sync); break;
-                FC_CASE(1) FC_CASE(2) FC_CASE(3) FC_CASE(4) FC_CASE(5) FC_CASE(6) FC_CASE(7) FC_CASE(8)
-#undef FC_CASE
-                default: return fail(-1, "mxm_em_loop_coded: H=%s%lld outside the one-launch loop's range", "", H);
-            }
+            const bool ok = dispatch_width<8>(cnch, [&](auto n) {
+                fits = launch_fused_coded<decltype(n)::value>(nwg, resident, s, coded, ldc, w, (int)H, (int)B, ln_cur, ln_new, props_cur,
+                                                              state, tol, (int)max_iter, (int)chunk, partial, ldpart, tbuf, sync);
+            });
+            if (!ok) return fail(-1, "mxm_em_loop_coded: H=%d outside the one-launch loop's range", H);
         } else if (fused_cols_eligible(R, (int)H, nwg) && fused_cols_fits(R, (int)H, (int)B, nwg, ws_bytes)) {
             // smallest matrices: columns split over the workgroups, the matrix in registers (workspace:
             // [sync][z partials nwg x ldz][c ldz][l1 partials 2 x nwg]; checked against ws_bytes above)
@@ -1643,33 +1668,26 @@ static int em_loop_fused(const double *P, int64_t ldp, const double *w, int64_t 
             double *l1part = cbuf + ldz;
             const int cp = ((int)H + nwg - 1) / nwg;
             const int rpt = (int)((R + FCOLS_THREADS - 1) / FCOLS_THREADS);
-#define FC_ARGS nwg, s, P, ldp, w, R, (int)H, (int)B, ln_cur, ln_new, props_cur, state, tol, (int)max_iter, (int)chunk, zpart, ldz, cbuf, l1part, sync
-            if (cp <= 12) {
-                if (rpt <= 1) fits = launch_fused_cols<12, 1>(FC_ARGS);
-                else if (rpt == 2) fits = launch_fused_cols<12, 2>(FC_ARGS);
-                else fits = launch_fused_cols<12, 3>(FC_ARGS);
-            } else if (cp <= 22) {
-                if (rpt <= 1) fits = launch_fused_cols<22, 1>(FC_ARGS);
-                else if (rpt == 2) fits = launch_fused_cols<22, 2>(FC_ARGS);
-                else fits = launch_fused_cols<22, 3>(FC_ARGS);
-            } else {
-                if (rpt <= 1) fits = launch_fused_cols<24, 1>(FC_ARGS);
-                else fits = launch_fused_cols<24, 2>(FC_ARGS);
-            }
-#undef FC_ARGS
+            // instances: 12, 22 or 24 columns per workgroup x 1 .. 3 rows per thread (24 columns: at most 2)
+            auto columns = [&](auto cpmax) {
+                constexpr int CP = decltype(cpmax)::value, MAX_RPT = CP == 24 ? 2 : 3;
+                (void)dispatch_width<MAX_RPT>(rpt < 1 ? 1 : (rpt > MAX_RPT ? MAX_RPT : rpt), [&](auto k) {
+                    fits = launch_fused_cols<CP, decltype(k)::value>(nwg, s, P, ldp, w, R, (int)H, (int)B, ln_cur, ln_new, props_cur, state,
+                                                                    tol, (int)max_iter, (int)chunk, zpart, ldz, cbuf, l1part, sync);
+                });
+            };
+            if (cp <= 12) columns(std::integral_constant<int, 12>{});
+            else if (cp <= 22) columns(std::integral_constant<int, 22>{});
+            else columns(std::integral_constant<int, 24>{});
         } else {
-            switch (nch) {
-#define FU_CASE(n) case n: fits = launch_fused<n>(nwg, s, P, ldp, w, R, (int)H, (int)B, ln_cur, ln_new, props_cur, state, tol, (int)max_iter, (int)chunk, partial, ldpart, tbuf, sync); break;
-                FU_CASE(1) FU_CASE(2) FU_CASE(3)
-#if FUSED_MAX_NCH > 3
-                FU_CASE(4) FU_CASE(5) FU_CASE(6)
-#endif
-#undef FU_CASE
-                default: return fail(-1, "mxm_em_loop: H=%s%lld outside the one-launch loop's range", "", H);
-            }
+            const bool ok = dispatch_width<FUSED_MAX_NCH>(nch, [&](auto n) {       // (the spill-free instances)
+                fits = launch_fused<decltype(n)::value>(nwg, s, P, ldp, w, R, (int)H, (int)B, ln_cur, ln_new, props_cur, state, tol,
+                                                        (int)max_iter, (int)chunk, partial, ldpart, tbuf, sync);
+            });
+            if (!ok) return fail(-1, "mxm_em_loop: H=%d outside the one-launch loop's range", H);
         }
         if (!fits) {
-            fail(-3, "mxm_em_loop: the one-launch loop's %s%lld workgroups cannot be co-resident on this device", "", nwg);
+            fail(-3, "mxm_em_loop: the one-launch loop's %d workgroups cannot be co-resident on this device", nwg);
             return MXM_FUSED_GAVE_UP;                                  // nothing was launched, nothing to undo
         }
         HIP_TRY(hipGetLastError());
@@ -1692,8 +1710,7 @@ static int enqueue_tile_iteration(const double *M, int64_t ldm, const double *P,
         if (nb == QB_BT && coded_batch_ok(coded, (int)H))
             return em_iter_coded_batched(coded, w, props_cur, (int)H, tile, state, colsum, (double *)ws, s, timed, &fin);
         for (int i = 0; i < nb; ++i) {
-            const int rc = em_iter_coded_one(coded, w, props_cur, (int)H, tile.s[i], state, colsum, (double *)ws, s, timed && i == 0, &fin);
-            if (rc != 0) return rc;
+            RC_TRY(em_iter_coded_one(coded, w, props_cur, (int)H, tile.s[i], state, colsum, (double *)ws, s, timed && i == 0, &fin));
         }
         return 0;
     } else if (linear) {
@@ -1718,52 +1735,98 @@ static int enqueue_tile_iteration(const double *M, int64_t ldm, const double *P,
     return 0;
 }
 
+// mxm_coded's contract, checked once by the loops over records (they block anyway; the one-launch loop has no room for
+// the in-kernel check the per-iteration kernel carries): wide_rows lists exactly the rows with 16-bit codes -- the loops
+// skip those in their main pass and take them from the list -- and, with_quads, quad_rows / byte_rows the rows with /
+// without quads.  The quad lists are looked at only when the wide list is sound.  `scratch`: two device words.
+static int records_lists_check(const mxm_coded *c, const char *who, void *scratch, hipStream_t s, bool with_quads) {
+    unsigned long long *chk = static_cast<unsigned long long *>(scratch), host[2] = {0, 0};
+    const dim3 grid(clamp_grid((c->R + 255) / 256, num_cu() * 4));
+    auto faults_of = [&](auto launch) -> int {          // host[] = what the kernel `launch` enqueues left in chk[]
+        HIP_TRY(hipMemsetAsync(chk, 0, sizeof(host), s));
+        launch();
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(host, chk, sizeof(host), hipMemcpyDeviceToHost, s));
+        HIP_TRY(hipStreamSynchronize(s));
+        return 0;
+    };
+    RC_TRY(faults_of([&] {
+        hipLaunchKernelGGL(coded_validate_kernel, grid, dim3(256), 0, s, c->ndist, c->R, c->wide_rows, c->n_wide, chk);
+    }));
+    if (host[1] != 0 || (long long)host[0] != (long long)c->n_wide)
+        return fail(-1, "%s: wide_rows must list exactly the rows with more than 256 values, ascending (%lld such rows, n_wide = %lld)",
+                    who, (long long)host[0], (long long)c->n_wide);
+    if (!with_quads) return 0;
+    RC_TRY(faults_of([&] {
+        hipLaunchKernelGGL(quad_validate_kernel, grid, dim3(256), 0, s, c->ndist, c->nquad, c->R, c->quad_rows, c->n_quad_rows,
+                           c->byte_rows, c->n_byte_rows, chk);
+    }));
+    if (host[1] != 0) return fail(-1, "%s: quad_rows / byte_rows must list the rows with / without quads, ascending", who);
+    return 0;
+}
+
+// What the per-iteration loop owns: its private stream, the event that orders it against the caller's, and the captured
+// chunk.  Released in this order: graph exec, graph, the stream (once it has drained), the event.
+struct loop_resources {
+    hipStream_t s = nullptr;
+    hipEvent_t ev = nullptr;
+    hipGraph_t graph = nullptr;
+    hipGraphExec_t exec = nullptr;
+    loop_resources() = default;
+    loop_resources(const loop_resources &) = delete;
+    loop_resources &operator=(const loop_resources &) = delete;
+    void drop_graph() {
+        if (exec != nullptr) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
+        if (graph != nullptr) { (void)hipGraphDestroy(graph); graph = nullptr; }
+    }
+    ~loop_resources() {
+        drop_graph();
+        if (s != nullptr) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
+        if (ev != nullptr) (void)hipEventDestroy(ev);
+    }
+};
+
 static int em_loop_impl(const double *M, int64_t ldm, const double *P, int64_t ldp, const double *w,
                         int64_t R, int32_t H, int32_t B, double *props_cur, double *ln_cur, double *ln_new,
                         double *colsum, mxm_em_state *state, double tol, int32_t max_iter,
                         int32_t check_every, void *ws, size_t ws_bytes, void *stream,
                         mxm_em_state *state_host, bool p_is_f32, const mxm_coded *coded = nullptr) {
-    if (state_host == nullptr || state == nullptr) return fail(-1, "mxm_em_loop: state pointers required%s", "");
-    if (R <= 0 || H <= 0 || B <= 0) return fail(-1, "mxm_em_loop: bad shape R=%s%lld H=%lld", "", R, H);
-    if (ws == nullptr || ws_bytes < mxm_workspace_bytes(R, H, B)) return fail(-1, "mxm_em_loop: workspace too small%s", "");
+    if (state_host == nullptr || state == nullptr) return fail(-1, "mxm_em_loop: state pointers required");
+    if (R <= 0 || H <= 0 || B <= 0) return fail(-1, "mxm_em_loop: bad shape R=%lld H=%d", (long long)R, H);
+    if (ws == nullptr || ws_bytes < mxm_workspace_bytes(R, H, B)) return fail(-1, "mxm_em_loop: workspace too small");
     if (check_every < 1) check_every = 1;
     if (T.progress != nullptr && check_every > T.progress_every) check_every = T.progress_every;
     hipStream_t caller = (hipStream_t)stream;
     (void)num_cu();                                    // device query outside any capture
-    HIP_TRY(hipMemcpyAsync(state_host, state, sizeof(mxm_em_state) * B, hipMemcpyDeviceToHost, caller));
-    HIP_TRY(hipStreamSynchronize(caller));
+    RC_TRY(read_state(state_host, state, B, caller));
     int running = 0;
     for (int b = 0; b < B; ++b) running += (state_host[b].done == 0) ? 1 : 0;
+    // The whole loop in persistent launches on the caller's stream (the host only waits; nothing is decided between
+    // iterations), where one of its forms applies:
+    //   records  restarts one after another over the records
+    //   narrow   the refinement EM on the contributors' columns: restarts one after another, the rows in registers
+    //   dense    a cache-resident linear matrix
+    fused_matrix fm = {fused_route::none, coded, M, ldm, P, ldp};
     if (coded != nullptr && running > 0 && max_iter > 0 && fused_coded_eligible(coded, (int)H, (int)B, ws_bytes, running)) {
-        // records: the whole loop in persistent launches on the caller's stream, restarts one after another.  A launch
-        // is kept to about half a second (a 10^7-row matrix takes 15 ms per iteration): `chunk` iterations each.
-        int chunk = T.fused_chunk > 0 ? T.fused_chunk : max_iter;
-        if (T.progress != nullptr && chunk > T.progress_every) chunk = T.progress_every;
-        const double est_us = (double)R * ((double)coded_ld(H) + 400.0) / 4.0e6 + 20.0;
-        const int cap = (int)std::max(8.0, 5.0e5 / est_us);
-        if (chunk > cap) chunk = cap;
-        const int frc = em_loop_fused(nullptr, 0, w, R, H, B, props_cur, ln_cur, ln_new, state, tol, max_iter, chunk, ws, ws_bytes,
-                                      caller, state_host, coded);
-        if (frc != MXM_FUSED_GAVE_UP) return frc;
-        if (T.loop_fused == 1) return -3;
+        fm.route = fused_route::records;
     } else if (int nrpt = 0; !p_is_f32 && coded == nullptr && M != nullptr && T.loop_fused != 0 && running > 0 && max_iter > 0 &&
                             !(P != nullptr && mxm_linear_supported(H)) && fused_narrow_grid(R, (int)H, &nrpt) > 0 &&
                             ws_bytes >= fused_sync_bytes() + fused_narrow_bytes((int)H, FNARROW_MAX_WG) + fused_snapshot_bytes(H, B) + 256) {
-        // narrow matrix (the refinement EM on the contributors' columns): the whole loop in one persistent launch,
-        // restarts one after another, the rows in registers
-        int chunk = T.fused_chunk > 0 ? T.fused_chunk : max_iter;
-        if (T.progress != nullptr && chunk > T.progress_every) chunk = T.progress_every;
-        const int frc = em_loop_fused(nullptr, 0, w, R, H, B, props_cur, ln_cur, ln_new, state, tol, max_iter, chunk, ws, ws_bytes,
-                                      caller, state_host, nullptr, M, ldm);
-        if (frc != MXM_FUSED_GAVE_UP) return frc;
-        if (T.loop_fused == 1) return -3;
+        fm.route = fused_route::narrow;
     } else if (fused_eligible(P, ldp, R, (int)H, (int)B, ws_bytes, p_is_f32, running)) {
-        // cache-resident matrix: the whole loop in one persistent launch on the caller's stream
-        // (the host only waits for it; nothing is decided between iterations)
+        fm.route = fused_route::dense;
+    }
+    if (fm.route != fused_route::none) {
         int chunk = T.fused_chunk > 0 ? T.fused_chunk : max_iter;
         if (T.progress != nullptr && chunk > T.progress_every) chunk = T.progress_every;     // someone is watching
-        const int frc = em_loop_fused(P, ldp, w, R, H, B, props_cur, ln_cur, ln_new, state, tol, max_iter, chunk, ws, ws_bytes,
-                                      caller, state_host);
+        if (fm.route == fused_route::records) {
+            // a launch is kept to about half a second (a 10^7-row matrix takes 15 ms per iteration)
+            const double est_us = (double)R * ((double)coded_ld(H) + 400.0) / 4.0e6 + 20.0;
+            const int cap = (int)std::max(8.0, 5.0e5 / est_us);
+            if (chunk > cap) chunk = cap;
+        }
+        const int frc = em_loop_fused(fm, w, R, H, B, props_cur, ln_cur, ln_new, state, tol, max_iter, chunk, ws, ws_bytes, caller,
+                                      state_host);
         // Gave up (grid not co-resident / starved): only mxm_set_loop_fused(1, ...) -- "whenever the shape allows" --
         // makes that an error; by default the same call goes on through the per-iteration kernels from the restored
         // state (another summation order: rounding-level differences, same stopping rule).
@@ -1779,13 +1842,11 @@ static int em_loop_impl(const double *M, int64_t ldm, const double *P, int64_t l
 
     // the loop runs on a private stream (the caller's may be the legacy default stream, which
     // cannot be captured); it is ordered after / before the caller's stream with events
-    hipStream_t s = nullptr;
-    hipEvent_t ev = nullptr;
-    HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
-    HIP_TRY(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
-    int rc = 0;
-    hipGraph_t graph = nullptr;
-    hipGraphExec_t exec = nullptr;
+    loop_resources own;
+    HIP_TRY(hipStreamCreateWithFlags(&own.s, hipStreamNonBlocking));
+    HIP_TRY(hipEventCreateWithFlags(&own.ev, hipEventDisableTiming));
+    const hipStream_t s = own.s;
+    const hipEvent_t ev = own.ev;
     std::vector<int> graph_key;
     // Restarts stop on different iterations, and a pass over the matrix costs nearly the same for one
     // restart as for a full tile.  Schedules (mxm_set_compact_restarts):
@@ -1797,15 +1858,9 @@ static int em_loop_impl(const double *M, int64_t ldm, const double *P, int64_t l
     // A tile names its restarts by index (mxm_slots, by value): nothing is moved in memory.  Each restart
     // counts its own iterations (finalize_kernel), so when it is scheduled changes nothing in its result.
     std::vector<int> order;                            // unfinished restarts, round-robin order
-#define LOOP_TRY(expr)                                                                        \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess) { rc = fail(-2, "HIP error: %s (line %lld)", hipGetErrorString(e_), __LINE__); goto done; } \
-    } while (0)
-    LOOP_TRY(hipEventRecord(ev, caller));
-    LOOP_TRY(hipStreamWaitEvent(s, ev, 0));
-    LOOP_TRY(hipMemcpyAsync(state_host, state, sizeof(mxm_em_state) * B, hipMemcpyDeviceToHost, s));
-    LOOP_TRY(hipStreamSynchronize(s));
+    HIP_TRY(hipEventRecord(ev, caller));
+    HIP_TRY(hipStreamWaitEvent(s, ev, 0));
+    RC_TRY(read_state(state_host, state, B, s));
     for (int b = 0; b < B; ++b)
         if (state_host[b].done == 0) order.push_back(b);
     if (max_iter <= 0) order.clear();
@@ -1862,52 +1917,39 @@ static int em_loop_impl(const double *M, int64_t ldm, const double *P, int64_t l
             std::vector<int> key(members);
             key.insert(key.end(), sizes.begin(), sizes.end());
             key.push_back((int)n);
-            if (exec == nullptr || key != graph_key) {
-                if (exec != nullptr) { (void)hipGraphExecDestroy(exec); exec = nullptr; }
-                if (graph != nullptr) { (void)hipGraphDestroy(graph); graph = nullptr; }
+            if (own.exec == nullptr || key != graph_key) {
+                own.drop_graph();
                 if (hipStreamBeginCapture(s, hipStreamCaptureModeThreadLocal) == hipSuccess) {
                     const int crc = enqueue_chunk();
-                    const hipError_t ee = hipStreamEndCapture(s, &graph);
-                    if (crc == 0 && ee == hipSuccess && hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0) == hipSuccess) {
+                    const hipError_t ee = hipStreamEndCapture(s, &own.graph);
+                    if (crc == 0 && ee == hipSuccess && hipGraphInstantiate(&own.exec, own.graph, nullptr, nullptr, 0) == hipSuccess) {
                         graph_key = key;
                     } else {
-                        exec = nullptr;                // capture unavailable: plain launches below
+                        own.exec = nullptr;            // capture unavailable: plain launches below
                         (void)hipGetLastError();
                     }
                 }
             }
-            if (exec != nullptr) {
-                LOOP_TRY(hipGraphLaunch(exec, s));
+            if (own.exec != nullptr) {
+                HIP_TRY(hipGraphLaunch(own.exec, s));
                 launched = true;
             }
         }
-        if (!launched) {
-            rc = enqueue_chunk();
-            if (rc != 0) goto done;
-        }
-        LOOP_TRY(hipMemcpyAsync(state_host, state, sizeof(mxm_em_state) * B, hipMemcpyDeviceToHost, s));
-        LOOP_TRY(hipStreamSynchronize(s));
+        if (!launched) RC_TRY(enqueue_chunk());
+        RC_TRY(read_state(state_host, state, B, s));
         for (int b = 0; b < B; ++b)
-            if (state_host[b].error != 0) {
-                rc = fail(-1, "mxm_em_loop: the records' wide_rows list does not match the rows with more than 256 values%s", "");
-                goto done;
-            }
+            if (state_host[b].error != 0)
+                return fail(-1, "mxm_em_loop: the records' wide_rows list does not match the rows with more than 256 values");
         if (T.progress != nullptr) T.progress(state_host, B, T.progress_user);
         std::vector<int> still;
         for (int b : order)
             if (state_host[b].done == 0) still.push_back(b);
         order.swap(still);
     }
-    LOOP_TRY(hipGetLastError());
-    LOOP_TRY(hipEventRecord(ev, s));
-    LOOP_TRY(hipStreamWaitEvent(caller, ev, 0));
-done:
-#undef LOOP_TRY
-    if (exec != nullptr) (void)hipGraphExecDestroy(exec);
-    if (graph != nullptr) (void)hipGraphDestroy(graph);
-    if (s != nullptr) { (void)hipStreamSynchronize(s); (void)hipStreamDestroy(s); }
-    if (ev != nullptr) (void)hipEventDestroy(ev);
-    return rc;
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(ev, s));
+    HIP_TRY(hipStreamWaitEvent(caller, ev, 0));
+    return 0;                                          // (`own` goes: exec, graph, the stream once it has drained, the event)
 }
 
 extern "C" int mxm_em_loop(const double *M, int64_t ldm, const double *P, int64_t ldp, const double *w,
@@ -1925,36 +1967,9 @@ extern "C" int mxm_em_loop_coded(const mxm_coded *c, const double *w, int32_t H,
                                  int32_t max_iter, int32_t check_every, void *ws, size_t ws_bytes, void *stream,
                                  mxm_em_state *state_host) {
     MXM_ENTER();
-    const int rc = coded_check(c, H, "mxm_em_loop_coded");
-    if (rc != 0) return rc;
-    if (ws == nullptr || ws_bytes < mxm_workspace_bytes(c->R, H, B)) return fail(-1, "mxm_em_loop_coded: workspace too small%s", "");
-    {
-        // The loop skips the rows with 16-bit codes in its main pass and takes them from `wide_rows`: the list must be
-        // exactly those rows.  This call blocks anyway, so it is checked once, here (the one-launch loop has no room for
-        // the in-kernel check the per-iteration kernel carries).
-        unsigned long long *chk = static_cast<unsigned long long *>(ws), host[2] = {0, 0};
-        hipStream_t s = (hipStream_t)stream;
-        HIP_TRY(hipMemsetAsync(chk, 0, 2 * sizeof(unsigned long long), s));
-        hipLaunchKernelGGL(coded_validate_kernel, dim3(clamp_grid((c->R + 255) / 256, num_cu() * 4)), dim3(256), 0, s, c->ndist, c->R,
-                           c->wide_rows, c->n_wide, chk);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(host, chk, sizeof(host), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (c->qrec != nullptr && host[1] == 0 && (long long)host[0] == (long long)c->n_wide) {   // ... and the quad dictionary's lists
-            unsigned long long qhost[2] = {0, 0};
-            HIP_TRY(hipMemsetAsync(chk, 0, 2 * sizeof(unsigned long long), s));
-            hipLaunchKernelGGL(quad_validate_kernel, dim3(clamp_grid((c->R + 255) / 256, num_cu() * 4)), dim3(256), 0, s, c->ndist,
-                               c->nquad, c->R, c->quad_rows, c->n_quad_rows, c->byte_rows, c->n_byte_rows, chk);
-            HIP_TRY(hipGetLastError());
-            HIP_TRY(hipMemcpyAsync(qhost, chk, sizeof(qhost), hipMemcpyDeviceToHost, s));
-            HIP_TRY(hipStreamSynchronize(s));
-            if (qhost[1] != 0)
-                return fail(-1, "mxm_em_loop_coded: quad_rows / byte_rows must list the rows with / without quads, ascending%s", "");
-        }
-        if (host[1] != 0 || (long long)host[0] != (long long)c->n_wide)
-            return fail(-1, "mxm_em_loop_coded: wide_rows must list exactly the rows with more than 256 values, ascending "
-                            "%s(%lld such rows, n_wide = %lld)", "", (long long)host[0], (long long)c->n_wide);
-    }
+    RC_TRY(coded_check(c, H, "mxm_em_loop_coded"));
+    if (ws == nullptr || ws_bytes < mxm_workspace_bytes(c->R, H, B)) return fail(-1, "mxm_em_loop_coded: workspace too small");
+    RC_TRY(records_lists_check(c, "mxm_em_loop_coded", ws, (hipStream_t)stream, c->qrec != nullptr));
     return em_loop_impl(nullptr, 0, nullptr, 0, w, c->R, H, B, props_cur, ln_cur, ln_new, colsum, state, tol, max_iter,
                         check_every, ws, ws_bytes, stream, state_host, false, c);
 }
@@ -1964,19 +1979,19 @@ extern "C" int mxm_samples_tile_rows(void) { return MXM_SAMPLES_TILE_ROWS; }
 
 extern "C" int64_t mxm_samples_plan(const int64_t *row0_host, int32_t S, mxm_sample_tile *tiles_host, int64_t cap,
                                     int32_t *tile0_host) {
-    if (row0_host == nullptr || S < 1) return fail(-1, "mxm_samples_plan: bad arguments%s (S=%lld)", "", S);
-    if (row0_host[0] != 0) return fail(-1, "mxm_samples_plan: row0[0] must be 0%s (it is %lld)", "", row0_host[0]);
+    if (row0_host == nullptr || S < 1) return fail(-1, "mxm_samples_plan: bad arguments (S=%d)", S);
+    if (row0_host[0] != 0) return fail(-1, "mxm_samples_plan: row0[0] must be 0 (it is %lld)", (long long)row0_host[0]);
     constexpr int64_t K = MXM_SAMPLES_TILE_ROWS;
     int64_t n = 0;
     for (int32_t s = 0; s < S; ++s) {
         const int64_t rows = row0_host[s + 1] - row0_host[s];
         if (rows <= 0)
-            return fail(-1, "mxm_samples_plan: row0 must ascend and no sample may be empty%s (sample %lld has %lld rows)", "", s, rows);
+            return fail(-1, "mxm_samples_plan: row0 must ascend and no sample may be empty (sample %d has %lld rows)", s, (long long)rows);
         if (tile0_host != nullptr) tile0_host[s] = (int32_t)n;
         const int64_t nt = (rows + K - 1) / K;
-        if (n + nt > 0x7fffffffll) return fail(-1, "mxm_samples_plan: more than 2^31 - 1 tiles%s", "");
+        if (n + nt > 0x7fffffffll) return fail(-1, "mxm_samples_plan: more than 2^31 - 1 tiles");
         if (tiles_host != nullptr) {
-            if (n + nt > cap) return fail(-1, "mxm_samples_plan: room for %s%lld tiles, sample %lld needs more", "", cap, s);
+            if (n + nt > cap) return fail(-1, "mxm_samples_plan: room for %lld tiles, sample %d needs more", (long long)cap, s);
             for (int64_t i = 0; i < nt; ++i) {
                 const int64_t left = rows - i * K;
                 tiles_host[n + i] = mxm_sample_tile{s, (int32_t)(left < K ? left : K), row0_host[s] + i * K};
@@ -2020,16 +2035,16 @@ extern "C" size_t mxm_samples_workspace_bytes(int64_t n_tiles, int32_t S, int32_
 // Everything the two entry points refuse before they touch the device; *n_tiles_out = the plan's size.
 static int samples_check(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, const char *who, int64_t *n_tiles_out) {
     if (c == nullptr || row0_host == nullptr || S < 1 || S > 65535)
-        return fail(-1, "%s: bad arguments (S = %lld; 1 .. 65535 samples)", who, S);
+        return fail(-1, "%s: bad arguments (S = %d; 1 .. 65535 samples)", who, S);
     if (c->R <= 0 || c->rec == nullptr || c->rec_off == nullptr || c->ndist == nullptr)
-        return fail(-1, "%s: coded matrix arrays missing (rows %lld)", who, c->R);
-    if ((H & 1) != 0 || H < 66 || H > 8192) return fail(-1, "%s: H = %lld: an even width in [66, 8192] is required", who, H);
+        return fail(-1, "%s: coded matrix arrays missing (rows %lld)", who, (long long)c->R);
+    if ((H & 1) != 0 || H < 66 || H > 8192) return fail(-1, "%s: H = %d: an even width in [66, 8192] is required", who, H);
     if (c->qrec != nullptr) return fail(-1, "%s: a quad dictionary is attached; the batched pass reads the records only", who);
-    if (c->R_rest != 0) return fail(-1, "%s: %lld rows without a record (the dense rest): such a sample runs on its own", who, c->R_rest);
+    if (c->R_rest != 0) return fail(-1, "%s: %lld rows without a record (the dense rest): such a sample runs on its own", who, (long long)c->R_rest);
     if (c->n_wide < 0 || (c->n_wide > 0 && c->wide_rows == nullptr)) return fail(-1, "%s: n_wide > 0 needs wide_rows", who);
     const int64_t n_tiles = mxm_samples_plan(row0_host, S, nullptr, 0, nullptr);
     if (n_tiles < 0) return -1;                           // (the plan's message stands)
-    if (row0_host[S] != c->R) return fail(-1, "%s: row0[S] = %lld, the matrix has %lld rows", who, row0_host[S], c->R);
+    if (row0_host[S] != c->R) return fail(-1, "%s: row0[S] = %lld, the matrix has %lld rows", who, (long long)row0_host[S], (long long)c->R);
     *n_tiles_out = n_tiles;
     return 0;
 }
@@ -2052,12 +2067,12 @@ static int samples_enqueue_pass(const mxm_coded *c, const double *w, const doubl
     const int ldc = coded_ld(H);
     const int nch = (ldc / 4 + SAMPLES_THREADS - 1) / SAMPLES_THREADS;
     const int64_t ldpart = part_ld(H);
-    switch (nch) {
-#define SMP_CASE(n) case n: hipLaunchKernelGGL((em_iter_samples_kernel<n, 4>), dim3((unsigned)n_tiles), dim3(SAMPLES_THREADS), 0, stream, c->rec, c->rec_off, c->ndist, ldc, w, props, H, (const mxm_sample_tile *)L.tiles, L.partial, ldpart, L.chk, (const mxm_em_state *)state); break;
-        SMP_CASE(1) SMP_CASE(2) SMP_CASE(3) SMP_CASE(4) SMP_CASE(5) SMP_CASE(6) SMP_CASE(7) SMP_CASE(8)
-#undef SMP_CASE
-        default: return fail(-1, "mxm_em_iter_samples: H=%s%lld outside the kernel's range", "", H);
-    }
+    const bool ok = dispatch_width<8>(nch, [&](auto n) {
+        hipLaunchKernelGGL((em_iter_samples_kernel<decltype(n)::value, 4>), dim3((unsigned)n_tiles), dim3(SAMPLES_THREADS), 0, stream, c->rec,
+                           c->rec_off, c->ndist, ldc, w, props, H, (const mxm_sample_tile *)L.tiles, L.partial, ldpart, L.chk,
+                           (const mxm_em_state *)state);
+    });
+    if (!ok) return fail(-1, "mxm_em_iter_samples: H=%d outside the kernel's range", H);
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(samples_colreduce_kernel, dim3((H + SAMPLES_COLRED_THREADS - 1) / SAMPLES_COLRED_THREADS, S),
                        dim3(SAMPLES_COLRED_THREADS), 0, stream, (const double *)L.partial, ldpart, (const int32_t *)L.tile0,
@@ -2070,14 +2085,12 @@ extern "C" int mxm_em_iter_samples(const mxm_coded *c, const int64_t *row0_host,
                                    int32_t H, mxm_em_state *state, double *colsum, void *ws, size_t ws_bytes, void *stream) {
     MXM_ENTER();
     int64_t n_tiles = 0;
-    const int rc = samples_check(c, row0_host, S, H, "mxm_em_iter_samples", &n_tiles);
-    if (rc != 0) return rc;
-    if (props == nullptr || colsum == nullptr || state == nullptr) return fail(-1, "mxm_em_iter_samples: bad arguments%s", "");
+    RC_TRY(samples_check(c, row0_host, S, H, "mxm_em_iter_samples", &n_tiles));
+    if (props == nullptr || colsum == nullptr || state == nullptr) return fail(-1, "mxm_em_iter_samples: bad arguments");
     if (ws == nullptr || ws_bytes < mxm_samples_workspace_bytes(n_tiles, S, H) || (reinterpret_cast<uintptr_t>(ws) & 15))
-        return fail(-1, "mxm_em_iter_samples: workspace too small (or not 16-byte aligned)%s", "");
+        return fail(-1, "mxm_em_iter_samples: workspace too small (or not 16-byte aligned)");
     const samples_ws L = samples_layout(ws, n_tiles, (int)S, (int)H);
-    const int urc = samples_upload_plan(row0_host, (int)S, n_tiles, L, (hipStream_t)stream);
-    if (urc != 0) return urc;
+    RC_TRY(samples_upload_plan(row0_host, (int)S, n_tiles, L, (hipStream_t)stream));
     return samples_enqueue_pass(c, w, props, (int)H, (int)S, n_tiles, L, state, colsum, (hipStream_t)stream);
 }
 
@@ -2087,34 +2100,18 @@ extern "C" int mxm_em_loop_samples(const mxm_coded *c, const int64_t *row0_host,
                                    mxm_em_state *state_host) {
     MXM_ENTER();
     int64_t n_tiles = 0;
-    const int rc = samples_check(c, row0_host, S, H, "mxm_em_loop_samples", &n_tiles);
-    if (rc != 0) return rc;
+    RC_TRY(samples_check(c, row0_host, S, H, "mxm_em_loop_samples", &n_tiles));
     if (props_cur == nullptr || ln_cur == nullptr || ln_new == nullptr || colsum == nullptr || state == nullptr || state_host == nullptr)
-        return fail(-1, "mxm_em_loop_samples: bad arguments%s", "");
+        return fail(-1, "mxm_em_loop_samples: bad arguments");
     if (ws == nullptr || ws_bytes < mxm_samples_workspace_bytes(n_tiles, S, H) || (reinterpret_cast<uintptr_t>(ws) & 15))
-        return fail(-1, "mxm_em_loop_samples: workspace too small (or not 16-byte aligned)%s", "");
+        return fail(-1, "mxm_em_loop_samples: workspace too small (or not 16-byte aligned)");
     if (check_every < 1) check_every = 1;
     if (T.progress != nullptr && check_every > T.progress_every) check_every = T.progress_every;
     hipStream_t s = (hipStream_t)stream;
     const samples_ws L = samples_layout(ws, n_tiles, (int)S, (int)H);
-    {
-        // mxm_coded's contract, checked once as mxm_em_loop_coded does: wide_rows lists exactly the rows with 16-bit codes
-        // (the passes here find them from ndist; the struct's other readers take the list's word)
-        unsigned long long *chk = reinterpret_cast<unsigned long long *>(L.partial), host[2] = {0, 0};
-        HIP_TRY(hipMemsetAsync(chk, 0, 2 * sizeof(unsigned long long), s));
-        hipLaunchKernelGGL(coded_validate_kernel, dim3(clamp_grid((c->R + 255) / 256, num_cu() * 4)), dim3(256), 0, s, c->ndist, c->R,
-                           c->wide_rows, c->n_wide, chk);
-        HIP_TRY(hipGetLastError());
-        HIP_TRY(hipMemcpyAsync(host, chk, sizeof(host), hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
-        if (host[1] != 0 || (long long)host[0] != (long long)c->n_wide)
-            return fail(-1, "mxm_em_loop_samples: wide_rows must list exactly the rows with more than 256 values, ascending "
-                            "%s(%lld such rows, n_wide = %lld)", "", (long long)host[0], (long long)c->n_wide);
-    }
-    const int urc = samples_upload_plan(row0_host, (int)S, n_tiles, L, s);
-    if (urc != 0) return urc;
-    HIP_TRY(hipMemcpyAsync(state_host, state, sizeof(mxm_em_state) * S, hipMemcpyDeviceToHost, s));
-    HIP_TRY(hipStreamSynchronize(s));
+    RC_TRY(records_lists_check(c, "mxm_em_loop_samples", L.partial, s, false));
+    RC_TRY(samples_upload_plan(row0_host, (int)S, n_tiles, L, s));
+    RC_TRY(read_state(state_host, state, S, s));
     auto running = [&]() {
         int n = 0;
         for (int b = 0; b < S; ++b) n += (state_host[b].done == 0) ? 1 : 0;
@@ -2128,16 +2125,13 @@ extern "C" int mxm_em_loop_samples(const mxm_coded *c, const int64_t *row0_host,
             if (state_host[b].done == 0) most_left = std::max<int64_t>(most_left, (int64_t)max_iter - state_host[b].iters);
         if (most_left > 0 && most_left < n) n = most_left;
         for (int64_t it = 0; it < n; ++it) {
-            const int prc = samples_enqueue_pass(c, w, props_cur, (int)H, (int)S, n_tiles, L, state, colsum, s);
-            if (prc != 0) return prc;
-            const int frc = mxm_m_finalize(colsum, ln_cur, ln_new, props_cur, H, S, tol, max_iter, state, s);
-            if (frc != 0) return frc;
+            RC_TRY(samples_enqueue_pass(c, w, props_cur, (int)H, (int)S, n_tiles, L, state, colsum, s));
+            RC_TRY(mxm_m_finalize(colsum, ln_cur, ln_new, props_cur, H, S, tol, max_iter, state, s));
         }
-        HIP_TRY(hipMemcpyAsync(state_host, state, sizeof(mxm_em_state) * S, hipMemcpyDeviceToHost, s));
-        HIP_TRY(hipStreamSynchronize(s));
+        RC_TRY(read_state(state_host, state, S, s));
         for (int b = 0; b < S; ++b)
             if (state_host[b].error != 0)
-                return fail(-1, "mxm_em_loop_samples: sample %s%lld has a row without a record (ndist outside 1 .. 1024)", "", b);
+                return fail(-1, "mxm_em_loop_samples: sample %d has a row without a record (ndist outside 1 .. 1024)", b);
         if (T.progress != nullptr) T.progress(state_host, S, T.progress_user);
     }
     return 0;
@@ -2167,10 +2161,10 @@ static void launch_estep_wide(const double *M, int64_t ldm, const double *w, con
 extern "C" int mxm_em_step(const double *M, int64_t ldm, const double *w, const double *ln_props, int64_t R,
                            int32_t H, double *out, int64_t ldo, int32_t mode, double *colsum, void *ws,
                            size_t ws_bytes, void *stream) {
-    if (R <= 0 || H <= 0 || ldm < H) return fail(-1, "mxm_em_step: bad shape%s", "");
-    if (out != nullptr && ldo < H) return fail(-1, "mxm_em_step: ldo < H%s", "");
+    if (R <= 0 || H <= 0 || ldm < H) return fail(-1, "mxm_em_step: bad shape");
+    if (out != nullptr && ldo < H) return fail(-1, "mxm_em_step: ldo < H");
     if (colsum != nullptr && (ws == nullptr || ws_bytes < mxm_workspace_bytes(R, H, 1)))
-        return fail(-1, "mxm_em_step: workspace too small%s", "");
+        return fail(-1, "mxm_em_step: workspace too small");
     const int64_t ldpart = part_ld(H);
     hipStream_t s = (hipStream_t)stream;
     double *partial = colsum ? (double *)ws : (double *)nullptr;
@@ -2184,13 +2178,10 @@ extern "C" int mxm_em_step(const double *M, int64_t ldm, const double *w, const 
     if (aligned && mxm_linear_supported(H) && nch <= (colsum != nullptr ? 10 : 13)) {
         // wide rows: one read + one write per cell, rows held in registers
         nwg = clamp_grid((R + 1) / 2, wide_cap);            // rows are dealt round-robin (row_deal)
-        switch (nch) {
-#define EW_CASE(n) case n: launch_estep_wide<n>(M, ldm, w, ln_props, R, (int)H, nwg, out, ldo, (int)mode, partial, ldpart, s); break;
-            EW_CASE(1) EW_CASE(2) EW_CASE(3) EW_CASE(4) EW_CASE(5) EW_CASE(6) EW_CASE(7) EW_CASE(8)
-            EW_CASE(9) EW_CASE(10) EW_CASE(11) EW_CASE(12) EW_CASE(13) EW_CASE(14) EW_CASE(15) EW_CASE(16)
-#undef EW_CASE
-            default: return fail(-1, "mxm_em_step: H=%s%lld outside the wide kernel's range", "", H);
-        }
+        const bool ok = dispatch_width<16>(nch, [&](auto n) {
+            launch_estep_wide<decltype(n)::value>(M, ldm, w, ln_props, R, (int)H, nwg, out, ldo, (int)mode, partial, ldpart, s);
+        });
+        if (!ok) return fail(-1, "mxm_em_step: H=%d outside the wide kernel's range", H);
     } else if (H <= MXM_NARROW_MAX_H) {
         const int rc = launch_narrow<false>(M, ldm, w, ln_props, R, (int)H, out, ldo, (int)mode, partial, ldpart,
                                             (const mxm_em_state *)nullptr, s, &nwg);
@@ -2202,37 +2193,31 @@ extern "C" int mxm_em_step(const double *M, int64_t ldm, const double *w, const 
             hipLaunchKernelGGL((estep_global_kernel<false>), dim3(nwg), dim3(ROW_THREADS), 0, s, M, ldm, w, ln_props, R, (int)H, out,
                                ldo, (int)mode, partial, ldpart, (const mxm_em_state *)nullptr, (const int64_t *)nullptr);
         } else {
-            if (lds > 60 * 1024 && raise_dynamic_lds(reinterpret_cast<const void *>(&estep_log_kernel<false>), lds, "estep_log_kernel") != hipSuccess)
-                return -2;
+            RC_TRY(dynamic_lds_ok(reinterpret_cast<const void *>(&estep_log_kernel<false>), lds, "estep_log_kernel"));
             hipLaunchKernelGGL((estep_log_kernel<false>), dim3(nwg), dim3(ROW_THREADS), lds, s, M, ldm, w, ln_props, R,
                                (int)H, out, ldo, (int)mode, partial, ldpart, (const mxm_em_state *)nullptr, (const int64_t *)nullptr);
         }
     }
     HIP_TRY(hipGetLastError());
-    if (colsum != nullptr) {
-        hipLaunchKernelGGL(colreduce_kernel, dim3((H + 63) / 64, 1), dim3(COLRED_THREADS), 0, s, (const double *)ws, ldpart, nwg,
-                           1, (int)H, (const double *)nullptr, colsum, (mxm_em_state *)nullptr, slots_from(0), wide_check{nullptr, 0, 0});
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    return colsum != nullptr ? reduce_one((const double *)ws, nwg, (int)H, colsum, nullptr, s) : 0;
 }
 
 extern "C" int mxm_log_normalize(const double *colsum, int32_t H, double *ln_new, void *stream) {
-    if (H <= 0) return fail(-1, "mxm_log_normalize: H <= 0%s", "");
+    if (H <= 0) return fail(-1, "mxm_log_normalize: H <= 0");
     hipLaunchKernelGGL(log_normalize_kernel, dim3(1), dim3(FIN_THREADS), 0, (hipStream_t)stream, colsum, (int)H, ln_new);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 extern "C" int mxm_l1_exp_diff(const double *a, const double *b, int32_t H, double *l1_out, void *stream) {
-    if (H <= 0) return fail(-1, "mxm_l1_exp_diff: H <= 0%s", "");
+    if (H <= 0) return fail(-1, "mxm_l1_exp_diff: H <= 0");
     hipLaunchKernelGGL(l1_exp_diff_kernel, dim3(1), dim3(FIN_THREADS), 0, (hipStream_t)stream, a, b, (int)H, l1_out);
     HIP_TRY(hipGetLastError());
     return 0;
 }
 
 extern "C" int mxm_add_scalar(double *x, int64_t ld, int64_t R, int32_t H, double delta, void *stream) {
-    if (R <= 0 || H <= 0 || ld < H) return fail(-1, "mxm_add_scalar: bad shape%s", "");
+    if (R <= 0 || H <= 0 || ld < H) return fail(-1, "mxm_add_scalar: bad shape");
     hipLaunchKernelGGL(add_scalar_kernel, dim3(clamp_grid(R, num_cu() * 8)), dim3(256), 0, (hipStream_t)stream, x, ld, R, (int)H, delta);
     HIP_TRY(hipGetLastError());
     return 0;
@@ -2241,7 +2226,7 @@ extern "C" int mxm_add_scalar(double *x, int64_t ld, int64_t R, int32_t H, doubl
 extern "C" int mxm_assign_reads(const double *X, int64_t ldx, const double *log_props, const int32_t *cols,
                                 int32_t nC, int64_t R, int32_t H, double log_min_fold, int32_t *assigned,
                                 void *stream) {
-    if (R <= 0 || H <= 0 || nC <= 0 || ldx < H) return fail(-1, "mxm_assign_reads: bad shape%s", "");
+    if (R <= 0 || H <= 0 || nC <= 0 || ldx < H) return fail(-1, "mxm_assign_reads: bad shape");
     hipLaunchKernelGGL(assign_reads_kernel, dim3((unsigned)((R + 255) / 256)), dim3(256), 0, (hipStream_t)stream, X,
                        ldx, log_props, cols, (int)nC, R, log_min_fold, assigned);
     HIP_TRY(hipGetLastError());
@@ -2250,12 +2235,12 @@ extern "C" int mxm_assign_reads(const double *X, int64_t ldx, const double *log_
 
 extern "C" int mxm_diag_stream_read(const void *src, size_t bytes, int32_t wg_per_cu, int32_t blocked, void *sink,
                                     void *stream) {
-    if (src == nullptr || sink == nullptr || bytes < 16 || wg_per_cu < 1) return fail(-1, "mxm_diag_stream_read: bad arguments%s", "");
+    if (src == nullptr || sink == nullptr || bytes < 16 || wg_per_cu < 1) return fail(-1, "mxm_diag_stream_read: bad arguments");
     if (blocked == 3) {
         // em_iter_coded_kernel's pattern: records of 5408 code bytes + 27 doubles (5624 bytes), two workgroups per CU
         const int code_bytes = 5408, tbl = 27, rec_bytes = code_bytes + tbl * 8;
         const int64_t recs = (int64_t)bytes / rec_bytes;
-        if (recs < 1) return fail(-1, "mxm_diag_stream_read: buffer smaller than one record%s", "");
+        if (recs < 1) return fail(-1, "mxm_diag_stream_read: buffer smaller than one record");
         hipLaunchKernelGGL(diag_stream_records_kernel<6>, dim3(clamp_grid(recs, num_cu() * wg_per_cu)), dim3(256), 0,
                            (hipStream_t)stream, (const uint8_t *)src, recs, rec_bytes, code_bytes, tbl, (unsigned int *)sink);
         HIP_TRY(hipGetLastError());
@@ -2265,7 +2250,7 @@ extern "C" int mxm_diag_stream_read(const void *src, size_t bytes, int32_t wg_pe
         // the EM kernel's pattern: rows of 5408 doubles (2704 x 16 B) dealt over one workgroup per CU
         const int row16 = 2704;
         const int64_t rows = (int64_t)(bytes / 16) / row16;
-        if (rows < 1) return fail(-1, "mxm_diag_stream_read: buffer smaller than one row%s", "");
+        if (rows < 1) return fail(-1, "mxm_diag_stream_read: buffer smaller than one row");
         hipLaunchKernelGGL(diag_stream_dealt_kernel<6>, dim3(clamp_grid(rows, num_cu() * wg_per_cu)), dim3(512), 0,
                            (hipStream_t)stream, (const double *)src, rows, row16, (unsigned int *)sink);
     } else if (blocked)
@@ -2279,11 +2264,10 @@ extern "C" int mxm_diag_stream_read(const void *src, size_t bytes, int32_t wg_pe
 }
 
 extern "C" int mxm_diag_stream_coded(const mxm_coded *c, int32_t H, int32_t wg_per_cu, void *sink, void *stream) {
-    const int rc = coded_check(c, H, "mxm_diag_stream_coded");
-    if (rc != 0) return rc;
-    if (sink == nullptr || wg_per_cu < 1) return fail(-1, "mxm_diag_stream_coded: bad arguments%s", "");
+    RC_TRY(coded_check(c, H, "mxm_diag_stream_coded"));
+    if (sink == nullptr || wg_per_cu < 1) return fail(-1, "mxm_diag_stream_coded: bad arguments");
     const int ldc = coded_ld(H);
-    if ((ldc / 4 + 255) / 256 != 6) return fail(-1, "mxm_diag_stream_coded: built for H in (5120, 6144]%s", "");
+    if ((ldc / 4 + 255) / 256 != 6) return fail(-1, "mxm_diag_stream_coded: built for H in (5120, 6144]");
     hipLaunchKernelGGL(diag_stream_coded_kernel<6>, dim3(clamp_grid(c->R, num_cu() * wg_per_cu)), dim3(256), 0, (hipStream_t)stream,
                        c->rec, c->rec_off, c->ndist, ldc, c->R, (unsigned int *)sink);
     HIP_TRY(hipGetLastError());
@@ -2291,10 +2275,9 @@ extern "C" int mxm_diag_stream_coded(const mxm_coded *c, int32_t H, int32_t wg_p
 }
 
 extern "C" int mxm_diag_stream_quads(const mxm_coded *c, int32_t H, int32_t wg_per_cu, void *sink, void *stream) {
-    const int rc = coded_check(c, H, "mxm_diag_stream_quads");
-    if (rc != 0) return rc;
+    RC_TRY(coded_check(c, H, "mxm_diag_stream_quads"));
     if (sink == nullptr || wg_per_cu < 1 || c->qrec == nullptr || c->n_quad_rows <= 0)
-        return fail(-1, "mxm_diag_stream_quads: a coded matrix with a quad dictionary required%s", "");
+        return fail(-1, "mxm_diag_stream_quads: a coded matrix with a quad dictionary required");
     hipLaunchKernelGGL(diag_stream_quads_kernel, dim3(clamp_grid(c->n_quad_rows, num_cu() * wg_per_cu)), dim3(QUAD_THREADS), 0,
                        (hipStream_t)stream, c->qrec, c->qoff, c->nquad, c->quad_rows, c->n_quad_rows, c->R, (unsigned int *)sink);
     HIP_TRY(hipGetLastError());
@@ -2303,9 +2286,9 @@ extern "C" int mxm_diag_stream_quads(const mxm_coded *c, int32_t H, int32_t wg_p
 
 extern "C" int mxm_row_argmax_votes(const double *X, int64_t ldx, const double *w, int64_t R, int32_t H,
                                     int32_t *best, double *votes, void *ws, size_t ws_bytes, void *stream) {
-    if (R <= 0 || H <= 0 || ldx < H) return fail(-1, "mxm_row_argmax_votes: bad shape%s", "");
+    if (R <= 0 || H <= 0 || ldx < H) return fail(-1, "mxm_row_argmax_votes: bad shape");
     if (votes != nullptr && (ws == nullptr || ws_bytes < mxm_workspace_bytes(R, H, 1)))
-        return fail(-1, "mxm_row_argmax_votes: workspace too small%s", "");
+        return fail(-1, "mxm_row_argmax_votes: workspace too small");
     // votes: every workgroup fills its own row of the scratch (one thread adds in row order), the
     // rows are summed in fixed order -- no float atomics, so fractional weights reproduce bit for bit
     double *part = votes != nullptr ? (double *)ws : (double *)nullptr;
@@ -2316,37 +2299,28 @@ extern "C" int mxm_row_argmax_votes(const double *X, int64_t ldx, const double *
         const int cap = num_cu() * 2 < MXM_MAX_WG ? num_cu() * 2 : MXM_MAX_WG;
         nwg = clamp_grid((R + 1) / 2, cap);
         const size_t lds = votes != nullptr ? (size_t)H * sizeof(double) : 0;
-        switch (nch) {
-#define AW_CASE(n) case n:                                                                                   \
-        if (lds > 60 * 1024 && /* with the static exchange buffers this passes the 64 KiB default */          \
-            raise_dynamic_lds(reinterpret_cast<const void *>(&row_argmax_wide_kernel<n>), lds,                \
-                              "row_argmax_wide_kernel") != hipSuccess)                                        \
-            return -2;                                                                                        \
-        hipLaunchKernelGGL((row_argmax_wide_kernel<n>), dim3(nwg), dim3(256), lds, (hipStream_t)stream, X, ldx, \
-                           w, R, (int)H, best, part, ldpart);                                                  \
-        break;
-            AW_CASE(1) AW_CASE(2) AW_CASE(3) AW_CASE(4) AW_CASE(5) AW_CASE(6) AW_CASE(7) AW_CASE(8)
-            AW_CASE(9) AW_CASE(10) AW_CASE(11) AW_CASE(12) AW_CASE(13) AW_CASE(14) AW_CASE(15) AW_CASE(16)
-#undef AW_CASE
-            default: return fail(-1, "mxm_row_argmax_votes: H=%s%lld outside the wide kernel's range", "", H);
-        }
+        int lrc = 0;
+        const bool ok = dispatch_width<16>(nch, [&](auto n) {
+            constexpr int NCH = decltype(n)::value;
+            // (with the static exchange buffers this passes the 64 KiB default)
+            lrc = dynamic_lds_ok(reinterpret_cast<const void *>(&row_argmax_wide_kernel<NCH>), lds, "row_argmax_wide_kernel");
+            if (lrc == 0)
+                hipLaunchKernelGGL((row_argmax_wide_kernel<NCH>), dim3(nwg), dim3(256), lds, (hipStream_t)stream, X, ldx, w, R, (int)H,
+                                   best, part, ldpart);
+        });
+        if (!ok) return fail(-1, "mxm_row_argmax_votes: H=%d outside the wide kernel's range", H);
+        if (lrc != 0) return lrc;
     } else {
         nwg = clamp_grid(R, num_cu() * 4 < MXM_MAX_WG ? num_cu() * 4 : MXM_MAX_WG);
         hipLaunchKernelGGL(row_argmax_votes_kernel, dim3(nwg), dim3(ROW_THREADS), 0, (hipStream_t)stream, X, ldx, w, R,
                            (int)H, best, part, ldpart);
     }
     HIP_TRY(hipGetLastError());
-    if (votes != nullptr) {
-        hipLaunchKernelGGL(colreduce_kernel, dim3((H + 63) / 64, 1), dim3(COLRED_THREADS), 0, (hipStream_t)stream,
-                           (const double *)part, ldpart, nwg, 1, (int)H, (const double *)nullptr, votes,
-                           (mxm_em_state *)nullptr, slots_from(0), wide_check{nullptr, 0, 0});
-        HIP_TRY(hipGetLastError());
-    }
-    return 0;
+    return votes != nullptr ? reduce_one(part, nwg, (int)H, votes, nullptr, (hipStream_t)stream) : 0;
 }
 
 extern "C" int mxm_first_seen(const int32_t *best, int64_t R, int32_t H, int64_t *first, void *stream) {
-    if (best == nullptr || first == nullptr || R < 0 || H <= 0) return fail(-1, "mxm_first_seen: bad arguments%s", "");
+    if (best == nullptr || first == nullptr || R < 0 || H <= 0) return fail(-1, "mxm_first_seen: bad arguments");
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(fill_u64_kernel, dim3(clamp_grid((H + 255) / 256, 64)), dim3(256), 0, s,
                        reinterpret_cast<unsigned long long *>(first), (int64_t)H, (unsigned long long)R);
@@ -2364,7 +2338,7 @@ extern "C" int mxm_first_seen(const int32_t *best, int64_t R, int32_t H, int64_t
 
 extern "C" int mxm_gather_columns(const double *M, int64_t ldm, int64_t R, int32_t H, const int32_t *cols, int32_t nC,
                                   double *out, int64_t ldo, void *stream) {
-    if (R < 0 || H <= 0 || nC <= 0 || ldm < H || ldo < nC) return fail(-1, "mxm_gather_columns: bad shape%s", "");
+    if (R < 0 || H <= 0 || nC <= 0 || ldm < H || ldo < nC) return fail(-1, "mxm_gather_columns: bad shape");
     if (R == 0) return 0;
     const int64_t want = (R * (int64_t)nC + 255) / 256;
     hipLaunchKernelGGL(gather_columns_kernel, dim3(clamp_grid(want, num_cu() * 16)), dim3(256), 0, (hipStream_t)stream,
@@ -2376,7 +2350,7 @@ extern "C" int mxm_gather_columns(const double *M, int64_t ldm, int64_t R, int32
 extern "C" int mxm_fold_logaddexp(double *acc, int64_t lda, const double *const *in_host, const int64_t *ld_in_host,
                                   int32_t n_in, int64_t R, int32_t H, double delta, void *stream) {
     if (R < 0 || H <= 0 || lda < H || n_in < 0 || n_in > FOLD_MAX_IN)
-        return fail(-1, "mxm_fold_logaddexp: bad shape (at most %s%lld inputs per call)", "", (long long)FOLD_MAX_IN);
+        return fail(-1, "mxm_fold_logaddexp: bad shape (at most %d inputs per call)", FOLD_MAX_IN);
     if (R == 0) return 0;
     fold_inputs in;
     bool vec = ((H & 1) == 0) && ((lda & 1) == 0) && ((reinterpret_cast<uintptr_t>(acc) & 15) == 0);
@@ -2384,7 +2358,7 @@ extern "C" int mxm_fold_logaddexp(double *acc, int64_t lda, const double *const 
         in.ptr[k] = k < n_in ? in_host[k] : nullptr;
         in.ld[k] = k < n_in ? ld_in_host[k] : 0;
         if (k < n_in) {
-            if (in.ptr[k] == nullptr || in.ld[k] < H) return fail(-1, "mxm_fold_logaddexp: bad input %s%lld", "", k);
+            if (in.ptr[k] == nullptr || in.ld[k] < H) return fail(-1, "mxm_fold_logaddexp: bad input %d", k);
             vec = vec && ((in.ld[k] & 1) == 0) && ((reinterpret_cast<uintptr_t>(in.ptr[k]) & 15) == 0);
         }
     }
@@ -2406,7 +2380,7 @@ extern "C" int mxm_fold_logaddexp(double *acc, int64_t lda, const double *const 
 // ------------------------------------------------------------------------------------------
 static int aln_columns_ok(const char *name, const mxm_aln_columns *cols) {
     if (cols == nullptr || cols->n_aln < 0) return fail(-1, "%s: bad arguments", name);
-    if (cols->n_aln > 0x7fffffffLL) return fail(-1, "%s: more than 2^31 - 1 alignments (%lld)", name, cols->n_aln);
+    if (cols->n_aln > 0x7fffffffLL) return fail(-1, "%s: more than 2^31 - 1 alignments (%lld)", name, (long long)cols->n_aln);
     if (cols->n_aln > 0 && (cols->ref_start == nullptr || cols->mapq == nullptr || cols->cig_ptr == nullptr ||
                             cols->cigar == nullptr || cols->seq_ptr == nullptr || cols->seq == nullptr))
         return fail(-1, "%s: ref_start, mapq, cig_ptr, cigar, seq_ptr and seq are required", name);
@@ -2436,8 +2410,8 @@ static int aln_walk_error(const char *name, unsigned long long err_host, const c
     if (err_host == ALN_ERR_NONE) return 0;
     const long long i = (long long)(err_host >> 2);
     const int kind = (int)(err_host & 3);
-    if (kind == 1) return fail(-4, "%s: the CIGAR of alignment %lld runs past its sequence", name, i);
-    if (kind == 2) return fail(-4, "%s: the CIGAR of alignment %lld holds an unknown operation", name, i);
+    if (kind == 1) return fail(-4, "%s: the CIGAR of alignment %lld runs past its sequence", name, (long long)i);
+    if (kind == 2) return fail(-4, "%s: the CIGAR of alignment %lld holds an unknown operation", name, (long long)i);
     snprintf(g_err, sizeof(g_err), "%s: alignment %lld %s", name, i, kind == 0 && kind0 != nullptr ? kind0 : kind3);
     return -1;
 }
@@ -2450,9 +2424,8 @@ static int observe_bases_impl(const char *name, const mxm_aln_columns *cols, con
                               uint32_t *counts, void *stream) {
     if (cols == nullptr || cols->n_aln < 0 || L < 0 || (L > 0 && n_labels > 0 && counts == nullptr))
         return fail(-1, "%s: bad arguments", name);
-    if (LABELLED && n_labels < 0) return fail(-1, "%s: n_labels < 0 (%lld)", name, n_labels);
-    const int rc = aln_columns_ok(name, cols);
-    if (rc) return rc;
+    if (LABELLED && n_labels < 0) return fail(-1, "%s: n_labels < 0 (%d)", name, n_labels);
+    RC_TRY(aln_columns_ok(name, cols));
     const int64_t n = cols->n_aln;
     if (n == 0) return 0;
     if (LABELLED && label == nullptr) return fail(-1, "%s: label is required", name);
@@ -2505,11 +2478,11 @@ extern "C" int mxm_observe_bases_labelled(const mxm_aln_columns *cols, const uin
 // ------------------------------------------------------------------------------------------
 extern "C" int mxm_consensus(const uint32_t *counts, int32_t n_labels, int64_t L, int64_t ref_len, int64_t min_cov,
                              int32_t strict, uint8_t *cons, uint8_t *tied, uint32_t *n_tied, void *stream) {
-    if (n_labels < 0 || L < 0 || ref_len < 0) return fail(-1, "mxm_consensus: bad shape%s", "");
+    if (n_labels < 0 || L < 0 || ref_len < 0) return fail(-1, "mxm_consensus: bad shape");
     const int64_t n = (int64_t)n_labels * ref_len;
     if (n == 0) return 0;
-    if (cons == nullptr || (counts == nullptr && L > 0)) return fail(-1, "mxm_consensus: counts and cons are required%s", "");
-    if ((reinterpret_cast<uintptr_t>(counts) & 15) != 0) return fail(-1, "mxm_consensus: counts must be 16-byte aligned%s", "");
+    if (cons == nullptr || (counts == nullptr && L > 0)) return fail(-1, "mxm_consensus: counts and cons are required");
+    if ((reinterpret_cast<uintptr_t>(counts) & 15) != 0) return fail(-1, "mxm_consensus: counts must be 16-byte aligned");
     hipLaunchKernelGGL(consensus_kernel, dim3(clamp_grid((n + ASM_THREADS - 1) / ASM_THREADS, num_cu() * 8)),
                        dim3(ASM_THREADS), 0, (hipStream_t)stream, counts, n_labels, L, ref_len, min_cov, (int)(strict != 0),
                        cons, tied, n_tied);
@@ -2520,10 +2493,10 @@ extern "C" int mxm_consensus(const uint32_t *counts, int32_t n_labels, int64_t L
 static int asm_rows_from(const char *name, const int32_t *rows_host, int32_t n_use, int64_t n_rows, asm_rows *out) {
     if (n_use < 0 || (n_use > 0 && rows_host == nullptr)) return fail(-1, "%s: bad participating rows", name);
     if (n_use > ASM_MAX_USE)
-        return fail(-1, "%s: %lld participating contributors, at most %lld (an owner is an int8)", name, n_use, ASM_MAX_USE);
+        return fail(-1, "%s: %d participating contributors, at most %d (an owner is an int8)", name, n_use, ASM_MAX_USE);
     memset(out, 0, sizeof(*out));
     for (int k = 0; k < n_use; ++k) {
-        if (rows_host[k] < 0 || rows_host[k] >= n_rows) return fail(-1, "%s: participating row %lld is no row", name, rows_host[k]);
+        if (rows_host[k] < 0 || rows_host[k] >= n_rows) return fail(-1, "%s: participating row %d is no row", name, rows_host[k]);
         out->row[k] = rows_host[k];
     }
     return 0;
@@ -2531,13 +2504,12 @@ static int asm_rows_from(const char *name, const int32_t *rows_host, int32_t n_u
 
 extern "C" int mxm_new_variants(const uint8_t *cons, int64_t ld, int32_t n_rows, const int32_t *rows_host, int32_t n_use,
                                 int64_t ref_len, uint32_t *newvar, uint32_t *n_new, void *stream) {
-    if (ref_len < 0 || ld < ref_len || n_rows < 0) return fail(-1, "mxm_new_variants: bad shape%s", "");
+    if (ref_len < 0 || ld < ref_len || n_rows < 0) return fail(-1, "mxm_new_variants: bad shape");
     asm_rows rows;
-    const int rc = asm_rows_from("mxm_new_variants", rows_host, n_use, n_rows, &rows);
-    if (rc) return rc;
+    RC_TRY(asm_rows_from("mxm_new_variants", rows_host, n_use, n_rows, &rows));
     if (ref_len == 0) return 0;
     if (newvar == nullptr || n_new == nullptr || (cons == nullptr && n_use > 0))
-        return fail(-1, "mxm_new_variants: cons, newvar and n_new are required%s", "");
+        return fail(-1, "mxm_new_variants: cons, newvar and n_new are required");
     hipLaunchKernelGGL(new_variants_kernel, dim3(clamp_grid((ref_len + ASM_THREADS - 1) / ASM_THREADS, num_cu() * 8)),
                        dim3(ASM_THREADS), 0, (hipStream_t)stream, cons, ld, rows, n_use, ref_len, newvar, n_new);
     HIP_TRY(hipGetLastError());
@@ -2548,8 +2520,7 @@ extern "C" int mxm_first_observed(const mxm_aln_columns *cols, const int32_t *la
                                   int32_t n_labels, int32_t min_mq, int32_t min_bq, int64_t ref_len, const uint8_t *tied,
                                   uint8_t *cons, void *stream) {
     const char *name = "mxm_first_observed";
-    const int rc = aln_columns_ok(name, cols);
-    if (rc) return rc;
+    RC_TRY(aln_columns_ok(name, cols));
     if (n_labels < 0 || ref_len < 0) return fail(-1, "%s: bad shape", name);
     const int64_t n = cols->n_aln, cells = (int64_t)n_labels * ref_len;
     if (n == 0 || cells == 0) return 0;
@@ -2577,11 +2548,9 @@ extern "C" int mxm_extend_assign(const mxm_aln_columns *cols, int32_t *label, in
                                  int32_t min_bq, const uint32_t *newvar, int64_t ref_len, int32_t *frag_state,
                                  int32_t *moved_owner, uint32_t *n_moved, void *stream) {
     const char *name = "mxm_extend_assign";
-    int rc = aln_columns_ok(name, cols);
-    if (rc) return rc;
+    RC_TRY(aln_columns_ok(name, cols));
     asm_rows rows;
-    rc = asm_rows_from(name, rows_host, n_use, n_rows, &rows);
-    if (rc) return rc;
+    RC_TRY(asm_rows_from(name, rows_host, n_use, n_rows, &rows));
     if (ref_len < 0 || cols->n_frag < 0 || round < 0) return fail(-1, "%s: bad shape", name);
     const int64_t n = cols->n_aln, n_frag = cols->n_frag;
     if (n == 0) return 0;

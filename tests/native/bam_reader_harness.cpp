@@ -5,12 +5,7 @@
 #include <stdlib.h>
 #include <vector>
 
-static thread_local char g_err[512] = "";
-static int fail(int code, const char *fmt, const char *a = "", long long b = 0, long long c = 0) {
-    snprintf(g_err, sizeof(g_err), fmt, a, b, c);
-    return code;
-}
-
+#include "error.hpp"
 #include "aln_encode.hpp"
 #include "bam_reader.hpp"
 

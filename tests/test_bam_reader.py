@@ -201,7 +201,7 @@ def test_reader_under_address_sanitizer(tmp_path, b17):
         pytest.skip("no g++")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     exe = str(tmp_path / "harness")
-    cmd = ["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+    cmd = ["g++", "-std=c++17", "-O1", "-g", "-Werror=format", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
            "-I" + os.path.join(root, "include"), "-I" + os.path.join(root, "mixemt_amd", "csrc"),
            os.path.join(root, "tests", "native", "bam_reader_harness.cpp"), "-o", exe, "-lz", "-lpthread"]
     proc = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)

@@ -742,3 +742,28 @@ def test_the_wide_rows_list_is_checked_where_it_is_used(b17):
     assert numpy.array_equal(best.cpu().numpy(), best_ref)
     dense = cm.dense().cpu().numpy() + ln_theta.cpu().numpy()[None, :]
     assert numpy.array_equal(best_ref, dense.argmax(axis=1))
+
+
+@pytest.mark.parametrize("n_haps", [66, 1024, 1025, 2048, 2049, 7169, 8192])
+def test_widths_at_the_edges_of_the_record_kernels_instances(n_haps):
+    """The record kernels come in instances of 1 .. 8 chunks of 256 threads x 4 code bytes: the first width, both sides of
+    the first two instance boundaries and both ends of the last instance.  Encode, decode, one iteration: the decoded
+    rows are the linearised matrix bit for bit, the column sums the dense pass's (summation order differs)."""
+    import torch
+    from mixemt_amd import em
+    n_rows = 5
+    rng = numpy.random.default_rng(n_haps)
+    few = rng.normal(-20.0, 6.0, size=(n_rows, 6))
+    mat = numpy.take_along_axis(few, rng.integers(0, 6, size=(n_rows, n_haps)), axis=1)
+    wts = rng.integers(1, 4, size=n_rows).astype(numpy.float64)
+    dense = em.EmPlan(mat, wts)
+    coded = em.EmPlan(mat, wts, storage="coded")                       # mxm_encode_rows
+    assert coded.coded is not None and coded.coded_rest == 0 and (_ndist(coded) <= 6).all()
+    dec = _decode(coded)                                               # mxm_decode_rows
+    assert torch.equal(dec.view(torch.int64), dense.lin[:, :n_haps].contiguous().view(torch.int64))
+    assert torch.equal(coded.rowmax, dense.rowmax)
+    props = torch.from_numpy(rng.dirichlet([1.0] * n_haps)[None, :]).to(dense.dev)
+    a, b = torch.zeros_like(props), torch.zeros_like(props)
+    dense.em_iter(props, torch.log(props), em.new_state(1, dense.dev), a)       # mxm_em_iter
+    coded.em_iter(props, torch.log(props), em.new_state(1, dense.dev), b)       # mxm_em_iter_coded
+    assert float(((a - b).abs() / a.abs()).max()) < 1e-12
