@@ -435,6 +435,9 @@ int mxm_em_loop_samples(const mxm_coded *c, const int64_t *row0_host, int32_t S,
                         int32_t max_iter, int32_t check_every, void *ws, size_t ws_bytes, void *stream,
                         mxm_em_state *state_host);
 
+/* The second half of a cohort run for the samples of one batched EM (votes, column gather, refinement EM, read assignment:
+ * mxm_votes_samples and its three siblings) is declared in mixemt_hip_samples_finish.h, included at the end of this header. */
+
 /*
  * The run_em inner loop for ONE rank -- em.py:126-143: repeats
  * {mxm_em_iter; mxm_m_finalize} on `stream` until every restart is done.
@@ -742,4 +745,5 @@ void mxm_exchange_destroy(mxm_exchange *x);
 #ifdef __cplusplus
 }
 #endif
+#include "mixemt_hip_samples_finish.h"
 #endif /* MIXEMT_HIP_H */

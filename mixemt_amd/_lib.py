@@ -184,6 +184,21 @@ SIGNATURES = {
                                           c_i64, c_i32, c_f64, c_ptr]),
 }
 
+# the batched second half of a cohort run (include/mixemt_hip_samples_finish.h: additions behind ABI version 603).  A table of its own: the
+# refusals of these entries are pinned in tests/test_samples_finish_host.py, those of SIGNATURES in tests/test_abi_messages.py
+FINISH_SIGNATURES = {
+    "mxm_samples_finish_workspace_bytes": (c_size, [c_i64, c_i32, c_i32]),
+    "mxm_votes_samples": (ctypes.c_int, [ctypes.POINTER(Coded), c_ptr, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                         c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "mxm_gather_columns_samples": (ctypes.c_int, [ctypes.POINTER(Coded), c_ptr, c_i32, c_i32, c_ptr, c_ptr, c_i32, c_ptr,
+                                                  c_ptr, c_size, c_ptr]),
+    "mxm_em_loop_samples_narrow": (ctypes.c_int, [ctypes.POINTER(Coded), c_ptr, c_i32, c_i32, c_ptr, c_i32, c_ptr, c_ptr,
+                                                  c_ptr, c_ptr, c_ptr, c_ptr, c_f64, c_i32, c_i32, c_ptr, c_ptr, c_size,
+                                                  c_ptr, ctypes.POINTER(EmState)]),
+    "mxm_assign_reads_samples": (ctypes.c_int, [ctypes.POINTER(Coded), c_ptr, c_i32, c_i32, c_ptr, c_i32, c_ptr, c_ptr,
+                                                c_ptr, c_ptr, c_ptr, c_ptr, c_f64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+}
+
 # the MXM_VERSION of include/mixemt_hip.h these signatures were written for; load() refuses any other
 ABI_VERSION = 603
 
@@ -220,7 +235,7 @@ def load():
     if have != ABI_VERSION:
         raise MixemtHipError("%s reports ABI version %s, this binding was written for %d: rebuild with "
                              "`python -m mixemt_amd.build --force`" % (LIB_PATH, have, ABI_VERSION))
-    for name, (restype, argtypes) in SIGNATURES.items():
+    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(FINISH_SIGNATURES.items()):
         try:
             fn = getattr(lib, name)
         except AttributeError:

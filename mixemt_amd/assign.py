@@ -502,3 +502,288 @@ def assign_reads(cols, contribs, em_results, haps, reads, args, dcols=None):
     labels = alignment_labels(frag_d, torch.from_numpy(ptr).to(dev), torch.from_numpy(group_frag).to(dev), row_label,
                               n_frag)
     return ContribReads(cols, labels, names, list(table), dcols, frag_d)
+
+
+# ---- the second half of a cohort run, batched (em.run_em_many's counterpart) ------------------------------------------
+FINISH_KMAX = 16                    # contributors a batched sample may have (the reduced matrix's widest row stride)
+FINISH_MAX_ROWS = 100000            # rows up to which one workgroup per sample was measured not slower than the per-sample
+                                    # refinement (S = 64: 0.10 / 0.15 / 0.44 / 1.00 of the per-sample loop's wall time at 600 /
+                                    # 4 600 / 3 * 10^4 / 10^5 rows, profiles/samples/finish.md); nothing larger was measured
+
+
+def _finish_route(n_rows, first_route, n_multi, max_rows, n_contribs=None, n_columns=None):
+    """'batch' or 'single' for one sample of finish_many: the per-sample functions take a sample whose first EM ran on
+    its own, every sample of a multi-run (the fold of the runs' posteriors, em.py:156, is theirs), one of more than
+    max_rows rows, and -- once its contributors are known -- one with more than FINISH_KMAX of them (or with a
+    haplogroup named twice, whose reduced matrix has fewer columns than contributors)."""
+    if first_route == "single" or n_multi > 1 or n_rows > max_rows:
+        return "single"
+    if n_contribs is not None and (n_contribs > FINISH_KMAX or (n_columns is not None and n_columns != n_contribs)):
+        return "single"
+    return "batch"
+
+
+def _finish_columns(contribs, hap_index):
+    """One sample's column plan: (cols, perm, sub_haps).  The reduced matrix keeps the contributors' columns in ASCENDING
+    haplogroup index (preprocess.py:247-251), the contributor table is by descending proportion: cols[i] is the
+    haplogroup index of reduced column i, perm[i] the ordinal of that haplogroup's contributor."""
+    idx = [hap_index[con[1]] for con in contribs]
+    order = sorted(range(len(idx)), key=lambda k: idx[k])
+    return [idx[k] for k in order], order, [contribs[k][1] for k in order]
+
+
+def _finish_tables(plans):
+    """The batch's [S][ld] tables from the batched samples' column plans: (ld, cols, ncol, perm) with ld = 4, 8 or 16 by
+    the largest number of columns among THESE samples; pad entries are 0."""
+    widest = max([len(cols) for cols, _, _ in plans] + [1])
+    if widest > FINISH_KMAX:
+        raise ValueError("finish_many: a batched sample may have at most %d contributors" % FINISH_KMAX)
+    ld = 4 if widest <= 4 else (8 if widest <= 8 else 16)
+    cols = numpy.zeros((len(plans), ld), dtype=numpy.int32)
+    perm = numpy.zeros((len(plans), ld), dtype=numpy.int32)
+    ncol = numpy.zeros(len(plans), dtype=numpy.int32)
+    for s, (c, p, _) in enumerate(plans):
+        ncol[s] = len(c)
+        cols[s, :len(c)] = c
+        perm[s, :len(c)] = p
+    return ld, cols, ncol, perm
+
+
+def _finish_inits(n_cols, refine_inits, alpha, n_multi=1):
+    """The refinements' initial proportions: n_cols[s] = columns of sample s's reduced matrix, None for a sample that is
+    not refined.  refine_inits None: init_props(K_s) from numpy's global legacy stream, sample after sample, refined
+    samples only (n_multi draws each).  A list of [n_multi][K_s] arrays (None where not refined)."""
+    from .em import init_props
+    if refine_inits is not None and len(refine_inits) != len(n_cols):
+        raise ValueError("finish_many: refine_inits needs one entry per sample")
+    out = []
+    for s, k in enumerate(n_cols):
+        if k is None:
+            out.append(None)
+        elif refine_inits is None:
+            out.append(numpy.stack([init_props(k, alpha=alpha) for _ in range(n_multi)]))
+        else:
+            init = numpy.atleast_2d(numpy.ascontiguousarray(refine_inits[s], dtype=numpy.float64))
+            if init.shape != (n_multi, k):
+                raise ValueError("finish_many: refine_inits[%d] must hold %d proportions, in the reduced matrix's column "
+                                 "order (ascending haplogroup index)" % (s, k))
+            out.append(init)
+    return out
+
+
+def _fixed_contributors(args, hap_index):
+    """args.contributors as haplogroup indexes (None when it is empty): ValueError for an unknown one, as
+    get_contributors raises it."""
+    fixed = getattr(args, "contributors", None)
+    if not fixed:
+        return None
+    cols = []
+    for con in fixed.split(","):
+        if con not in hap_index:
+            raise ValueError("Unknown haplogroup '%s'" % (con))
+        cols.append(hap_index[con])
+    return cols
+
+
+def _finish_check(samples, results, haplogroups, args, obs):
+    """finish_many's argument checks (host only); returns the haplogroup -> index table."""
+    from .preprocess import CodedMatrix
+    if not samples or len(results) != len(samples):
+        raise ValueError("finish_many: one result of run_em_many per sample is needed (%d samples, %d results)"
+                         % (len(samples), len(results)))
+    mats = [pair[0] for pair in samples]
+    if any(not isinstance(m, CodedMatrix) for m in mats) or any(m.rec.data_ptr() != mats[0].rec.data_ptr() for m in mats):
+        raise ValueError("finish_many: the samples must be views of ONE record buffer (preprocess.build_em_records_many's "
+                         "matrix and cm.rows(lo, hi) of it)")
+    hap_index = {}
+    for i, hap in enumerate(haplogroups):
+        hap_index.setdefault(hap, i)
+    if mats[0].n_haps != len(haplogroups):
+        raise ValueError("finish_many: %d haplogroups for matrices of %d columns" % (len(haplogroups), mats[0].n_haps))
+    fixed = _fixed_contributors(args, hap_index)
+    if args.var_check and fixed is None:
+        if obs is None:
+            raise ValueError("finish_many: args.var_check without args.contributors needs obs= (one observe.ObservedBases "
+                             "per sample) and phylo=")
+        if len(obs) != len(samples):
+            raise ValueError("finish_many: obs needs one entry per sample (%d samples, %d entries)" % (len(samples), len(obs)))
+    return hap_index, fixed
+
+
+def _empty_finish(route, order, votes):
+    return {"contribs": [], "vote_order": order, "votes": votes, "sub_haps": [], "refined": None,
+            "assigned": AssignedReads(numpy.zeros(0, dtype=numpy.int32), []), "row_label": numpy.zeros(0, dtype=numpy.int32),
+            "route": route, "posterior": None}
+
+
+def _finish_single(cm, wts, res, contribs, order, votes, haplogroups, hap_index, args, init, want_posterior):
+    """One sample through the existing per-sample functions (reduce_em_records -> run_em_ex -> update_contribs ->
+    _assign_rows; unrefined: the full-width posterior of the first EM), with finish_many's result dict."""
+    from . import em, preprocess
+    if not contribs:
+        return _empty_finish("single", order, votes)
+    _, _, sub_haps = _finish_columns(contribs, hap_index)
+    refined = posterior = None
+    if args.refine_ests:
+        sub, sub_haps = preprocess.reduce_em_records(cm, haplogroups, contribs)
+        run = em.run_em_ex(sub, wts, args, inits=init)
+        contribs = update_contribs(contribs, (run["props"], run["read_mix"]), sub_haps)
+        table, assigned = _assign_rows(contribs, (run["props"], run["read_mix"]), sub_haps, cm.n_rows, args.min_fold)
+        refined = {key: run[key] for key in ("props", "iters", "done", "l1", "inits")}
+        posterior = run["read_mix"] if want_posterior else None
+    else:
+        read_mix = em.RecordsPosterior(cm, res["ln_theta_k"]).dense()
+        table, assigned = _assign_rows(contribs, (res["props"], read_mix), haplogroups, cm.n_rows, args.min_fold)
+    label = numpy.zeros(cm.n_rows, dtype=numpy.int32) if assigned is None else assigned.cpu().numpy()
+    return {"contribs": contribs, "vote_order": order, "votes": votes, "sub_haps": sub_haps, "refined": refined,
+            "assigned": table, "row_label": label, "route": "single", "posterior": posterior}
+
+
+def _finish_batch(samples, wts_d, ids):
+    """em.SampleFinish over the samples `ids` (their record offsets back to back; nothing of the records is copied)."""
+    from . import em
+    mats = [samples[i][0] for i in ids]
+    row0 = numpy.concatenate([[0], numpy.cumsum([m.n_rows for m in mats])]).astype(numpy.int64)
+    return em.SampleFinish(mats[0].rec, torch.cat([m.rec_off for m in mats]), torch.cat([m.ndist for m in mats]),
+                           torch.cat([wts_d[i] for i in ids]), torch.cat([m.rowmax for m in mats]), row0, mats[0].n_haps)
+
+
+def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refine_inits=None, max_rows=None,
+                want_posterior=False):
+    """
+    What mixemt reports for a sample after its EM (bin/mixemt:298-323: get_contributors, the refinement run_em on the
+    contributors' columns with update_contribs, assign_read_indexes) for ALL samples of one em.run_em_many call in
+    batched device passes, instead of a Python loop of get_contributors_records / reduce_em_records / run_em /
+    _assign_rows over them.  Opt-in; the per-sample functions are unchanged.
+    samples: run_em_many's list of (preprocess.CodedMatrix, weights), views of ONE record buffer
+        (preprocess.build_em_records_many's matrix and cm.rows(lo, hi) of it); anything else is a ValueError.
+    results: run_em_many's list (props and ln_theta_k are read).
+    args: the reference's namespace -- min_reads, contributors, var_check (with min_var_reads, frac_var_reads, var_count,
+        var_fraction, verbose), refine_ests, min_fold, tolerance, max_iter, init_alpha, n_multi.
+    phylo / obs: for the variant check (check_contrib_phy_vars, run per sample on the host as it is): obs is a list with
+        one observe.ObservedBases per sample, required when args.var_check is set and args.contributors is empty.
+    refine_inits: None draws init_props(K_s) from numpy's global legacy stream, sample after sample, only for the samples
+        that are refined -- NOT the stream position a Python loop over whole samples would reach (there the first EM's
+        draw of sample s + 1 follows the refinement draw of sample s); or a list with [K_s] proportions per sample (None
+        where nothing is refined), in the REDUCED matrix's column order: ascending haplogroup index (preprocess.py:247-251),
+        not contributor order.
+    max_rows: a sample of more rows takes the per-sample route (default FINISH_MAX_ROWS).
+    Returns one dict per sample:
+        contribs    [[hapNN, haplogroup, proportion], ...] as get_contributors and update_contribs leave it
+        vote_order, votes   what vote_table_from_records returns (haplogroups in first-seen order, unweighted votes [H])
+        sub_haps    the reduced matrix's column names
+        refined     {props, iters, done, l1, inits} of the refinement run (batch route: also ln_theta_k and ln_theta_next,
+                    the loop's own log vectors); None when args.refine_ests is false (the rows are then assigned from
+                    the first EM's posterior, contributors' columns only) or nothing contributes
+        assigned    an AssignedReads (contributor order); row_label: its int32 [R_s] ordinals, -1 = unassigned
+        route       "batch", or "single": the sample went through the per-sample functions -- its first EM ran on its
+                    own, args.n_multi > 1 (the fold of several runs' posteriors, em.py:156, stays with the per-sample
+                    path), more than max_rows rows, or more than 16 contributors
+        posterior   always present; None unless want_posterior is set (an addition to mixemt's own outputs, for tests and
+                    for `-s`-like dumps): then the reduced posterior under theta_k ([R_s][K_s], device), refined samples only
+    A sample without a contributor returns contribs == [], refined None and an empty AssignedReads; nothing is launched
+    for it.  A sample with ONE contributor is still refined on R x 1, as bin/mixemt:311-320 does.
+    """
+    from . import em
+    hap_index, fixed = _finish_check(samples, results, haplogroups, args, obs)
+    n = len(samples)
+    n_multi = int(getattr(args, "n_multi", 1))
+    max_rows = FINISH_MAX_ROWS if max_rows is None else int(max_rows)
+    dev = require_gpu()
+    wts_d = [as_device(w, torch.float64, dev).reshape(-1) for _, w in samples]
+    if any(int(w.numel()) != m.n_rows for w, (m, _) in zip(wts_d, samples)):
+        raise ValueError("finish_many: weights do not match the samples' rows")
+    route = [_finish_route(samples[s][0].n_rows, results[s].get("route"), n_multi, max_rows) for s in range(n)]
+    contribs, orders, counts = [None] * n, [None] * n, [None] * n
+    obs_of = (lambda s: obs[s]) if obs is not None else (lambda s: None)
+
+    # ---- votes and contributor tables ----
+    voted = [s for s in range(n) if route[s] == "batch"]
+    first_batch = lse_all = None
+    if voted:
+        first_batch = _finish_batch(samples, wts_d, voted)
+        ln_props = numpy.stack([numpy.atleast_2d(results[s]["ln_theta_k"])[0] for s in voted])
+        _, votes_w, counts_h, first_h, lse_all, errors = first_batch.votes(ln_props, want_lse=not args.refine_ests)
+        for j, s in enumerate(voted):
+            if errors[j]:
+                raise ValueError("finish_many: sample %d has a row without a record (ndist outside 1 .. 1024)" % s)
+            n_rows = samples[s][0].n_rows
+            seen = numpy.flatnonzero(first_h[j] < n_rows)
+            order = seen[numpy.argsort(first_h[j][seen], kind="stable")]
+            orders[s], counts[s] = order, counts_h[j].astype(numpy.float64)
+            found = [int(h) for h in order if votes_w[j][h] >= args.min_reads]
+            contribs[s] = _contributor_table(phylo, obs_of(s), haplogroups, results[s]["props"], lambda: found, args)
+    for s in range(n):
+        if route[s] == "single":
+            cm = samples[s][0]
+            contribs[s] = get_contributors_records(phylo, obs_of(s), haplogroups, wts_d[s], results[s]["props"], cm,
+                                                   results[s]["ln_theta_k"], args)
+            orders[s], counts[s] = vote_table_from_records(cm, results[s]["ln_theta_k"], None)
+
+    # ---- column plans; the samples that leave the batch now that their contributors are known ----
+    plans = [None] * n
+    for s in range(n):
+        if contribs[s]:
+            plans[s] = _finish_columns(contribs[s], hap_index)
+            if route[s] == "batch":
+                route[s] = _finish_route(samples[s][0].n_rows, results[s].get("route"), n_multi, max_rows,
+                                         len(contribs[s]), len(set(plans[s][0])))
+    refine = bool(args.refine_ests)
+    inits = _finish_inits([len(set(plans[s][0])) if (refine and plans[s] is not None) else None for s in range(n)],
+                          refine_inits, args.init_alpha, n_multi)
+
+    out = [None] * n
+    for s in range(n):
+        if not contribs[s]:
+            out[s] = _empty_finish(route[s], orders[s], counts[s])
+        elif route[s] == "single":
+            out[s] = _finish_single(samples[s][0], wts_d[s], results[s], contribs[s], orders[s], counts[s], haplogroups,
+                                    hap_index, args, inits[s], want_posterior)
+    ids = [s for s in range(n) if out[s] is None]
+    if not ids:
+        return out
+
+    # ---- the batch: gather, refinement loop, assignment ----
+    batch = first_batch if ids == voted else _finish_batch(samples, wts_d, ids)
+    ld, cols, ncol, perm = _finish_tables([plans[s] for s in ids])
+    mat = batch.gather(cols, ncol, ld)
+    ln_theta = numpy.full((len(ids), ld), -numpy.inf)
+    log_props = numpy.full((len(ids), ld), -numpy.inf)
+    refined = [None] * len(ids)
+    lse = None
+    if refine:
+        ln_cur, ln_new, states = batch.em_loop(mat, ld, ncol, [inits[s][0] for s in ids], args.tolerance, args.max_iter)
+        for j, s in enumerate(ids):
+            k = int(ncol[j])
+            props = numpy.exp(ln_new[j, :k])                                    # em.py:163 with one run
+            refined[j] = {"props": props, "iters": [states[j][1]], "done": [states[j][0]], "l1": [states[j][2]],
+                          "inits": inits[s], "ln_theta_k": ln_cur[j, :k].copy(), "ln_theta_next": ln_new[j, :k].copy()}
+            contribs[s] = update_contribs(contribs[s], (props, None), plans[s][2])
+            ln_theta[j, :k] = ln_cur[j, :k]
+            with numpy.errstate(divide="ignore"):
+                log_props[j, :k] = numpy.log(props)
+    else:
+        # the first EM's posterior, contributors' columns only: its full-width row normaliser comes from the vote pass
+        if ids == voted:
+            lse = lse_all
+        else:
+            start = numpy.concatenate([[0], numpy.cumsum([samples[s][0].n_rows for s in voted])])
+            at = {s: j for j, s in enumerate(voted)}
+            lse = torch.cat([lse_all[int(start[at[s]]):int(start[at[s] + 1])] for s in ids])
+        for j, s in enumerate(ids):
+            k = int(ncol[j])
+            ln_theta[j, :k] = numpy.atleast_2d(results[s]["ln_theta_k"])[0][cols[j, :k]]
+            with numpy.errstate(divide="ignore"):
+                log_props[j, :k] = numpy.log(numpy.asarray(results[s]["props"], dtype=numpy.float64)[cols[j, :k]])
+    assigned, post = batch.assign(mat, ld, ncol, perm, ln_theta, log_props, lse, args.min_fold,
+                                  want_post=want_posterior and refine)
+    labels = assigned.cpu().numpy()
+    for j, s in enumerate(ids):
+        lo, hi = int(batch.row0[j]), int(batch.row0[j + 1])
+        names = [con[0] for con in contribs[s]]
+        label = labels[lo:hi].copy()
+        out[s] = {"contribs": contribs[s], "vote_order": orders[s], "votes": counts[s], "sub_haps": plans[s][2],
+                  "refined": refined[j], "assigned": AssignedReads(label, names),
+                  "row_label": label, "route": "batch",
+                  "posterior": post[lo:hi, :int(ncol[j])] if post is not None else None}
+    return out

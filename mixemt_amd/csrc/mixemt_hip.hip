@@ -28,6 +28,7 @@
 //   coded_kernels.hpp   encode_rows_kernel, em_iter_coded_kernel (row-dictionary storage: one byte per cell + the row's distinct values)
 //   fused_coded_kernels.hpp  em_fused_coded_kernel (the whole EM loop over records in one persistent launch)
 //   fused_narrow_kernels.hpp  em_fused_narrow_kernel (the same for the refinement EM's few columns: the matrix in registers)
+//   samples_finish_kernels.hpp  votes, column gather, refinement EM loop and read assignment of many samples per launch
 //   samples_kernels.hpp em_iter_samples_kernel, samples_colreduce_kernel (the EM iteration of many samples in one launch: a tile of
 //                       one sample's rows per workgroup)
 //   aln_encode.hpp      HOST code: mxm_aln_encode, the batched alignment front end (process_reads + reduce_reads + row order)
@@ -71,6 +72,7 @@
 #include "fused_coded_kernels.hpp"
 #include "fused_narrow_kernels.hpp"
 #include "samples_kernels.hpp"
+#include "samples_finish_kernels.hpp"
 #include "exchange.hpp"
 #include "aln_walk.hpp"
 #include "observe_kernels.hpp"
@@ -2134,6 +2136,226 @@ extern "C" int mxm_em_loop_samples(const mxm_coded *c, const int64_t *row0_host,
                 return fail(-1, "mxm_em_loop_samples: sample %d has a row without a record (ndist outside 1 .. 1024)", b);
         if (T.progress != nullptr) T.progress(state_host, S, T.progress_user);
     }
+    return 0;
+}
+
+// ---- the second half of a cohort run: votes, column gather, refinement EM, read assignment (samples_finish_kernels.hpp) ----
+// scratch layout: [tile table][row0, S + 1][cols, S x ld][ncol, S][perm, S x ld]
+struct finish_ws {
+    mxm_sample_tile *tiles;
+    int64_t *row0;
+    int32_t *cols, *ncol, *perm;
+    size_t bytes;
+};
+static finish_ws finish_layout(void *ws, int64_t n_tiles, int S, int ld) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    finish_ws L;
+    char *base = static_cast<char *>(ws);
+    size_t at = 0;
+    L.tiles = reinterpret_cast<mxm_sample_tile *>(base + at);
+    at += up((size_t)n_tiles * sizeof(mxm_sample_tile));
+    L.row0 = reinterpret_cast<int64_t *>(base + at);
+    at += up((size_t)(S + 1) * sizeof(int64_t));
+    L.cols = reinterpret_cast<int32_t *>(base + at);
+    at += up((size_t)S * ld * sizeof(int32_t));
+    L.ncol = reinterpret_cast<int32_t *>(base + at);
+    at += up((size_t)S * sizeof(int32_t));
+    L.perm = reinterpret_cast<int32_t *>(base + at);
+    at += up((size_t)S * ld * sizeof(int32_t));
+    L.bytes = at;
+    return L;
+}
+extern "C" size_t mxm_samples_finish_workspace_bytes(int64_t n_tiles, int32_t S, int32_t ld) {
+    if (n_tiles <= 0 || S <= 0 || ld < 0) return 0;
+    return finish_layout(nullptr, n_tiles, (int)S, (int)ld).bytes;
+}
+
+// What the four entry points refuse beyond samples_check: the reduced matrix's stride and every sample's column count
+// (cols_host / perm_host nullable: the entry does not take them).
+static int finish_cols_check(const char *who, int32_t S, int32_t H, int32_t ld, const int32_t *ncol_host, const int32_t *cols_host,
+                             const int32_t *perm_host) {
+    if (ld != 4 && ld != 8 && ld != 16) return fail(-1, "%s: ld = %d: the reduced matrix's row stride must be 4, 8 or 16", who, ld);
+    if (ncol_host == nullptr) return fail(-1, "%s: bad arguments (ncol_host missing)", who);
+    for (int32_t s = 0; s < S; ++s) {
+        const int32_t k = ncol_host[s];
+        if (k < 0 || k > ld) return fail(-1, "%s: sample %d has ncol = %d outside [0, %d]", who, s, k, ld);
+        for (int32_t i = 0; i < k; ++i) {
+            if (cols_host != nullptr && (cols_host[(int64_t)s * ld + i] < 0 || cols_host[(int64_t)s * ld + i] >= H))
+                return fail(-1, "%s: sample %d, column %d: haplogroup index %d outside [0, %d)", who, s, i,
+                            cols_host[(int64_t)s * ld + i], H);
+            if (perm_host != nullptr && (perm_host[(int64_t)s * ld + i] < 0 || perm_host[(int64_t)s * ld + i] >= k))
+                return fail(-1, "%s: sample %d, column %d: contributor ordinal %d outside [0, %d)", who, s, i,
+                            perm_host[(int64_t)s * ld + i], k);
+        }
+    }
+    return 0;
+}
+
+static int finish_ws_check(const char *who, const void *ws, size_t ws_bytes, int64_t n_tiles, int32_t S, int32_t ld) {
+    if (ws == nullptr || ws_bytes < mxm_samples_finish_workspace_bytes(n_tiles, S, ld) || (reinterpret_cast<uintptr_t>(ws) & 15))
+        return fail(-1, "%s: workspace too small (or not 16-byte aligned)", who);
+    return 0;
+}
+
+// the plan and the per-sample tables into the workspace, ordered on `stream` (from pageable memory: the runtime has
+// taken the bytes when the call returns)
+static int finish_upload(const int64_t *row0_host, int S, int64_t n_tiles, int ld, const int32_t *ncol_host, const int32_t *cols_host,
+                         const int32_t *perm_host, const finish_ws &L, hipStream_t stream) {
+    static thread_local std::vector<mxm_sample_tile> tiles;
+    tiles.resize((size_t)n_tiles);
+    if (mxm_samples_plan(row0_host, S, tiles.data(), n_tiles, nullptr) != n_tiles) return -1;
+    HIP_TRY(hipMemcpyAsync(L.tiles, tiles.data(), (size_t)n_tiles * sizeof(mxm_sample_tile), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemcpyAsync(L.row0, row0_host, ((size_t)S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    if (ncol_host != nullptr) HIP_TRY(hipMemcpyAsync(L.ncol, ncol_host, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    if (cols_host != nullptr) HIP_TRY(hipMemcpyAsync(L.cols, cols_host, (size_t)S * ld * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    if (perm_host != nullptr) HIP_TRY(hipMemcpyAsync(L.perm, perm_host, (size_t)S * ld * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    return 0;
+}
+
+extern "C" int mxm_votes_samples(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, const double *w,
+                                 const double *ln_props, const double *props, const double *rowmax, int32_t *best, double *votes,
+                                 int64_t *counts, int64_t *first, double *lse, mxm_em_state *state, void *ws, size_t ws_bytes,
+                                 void *stream) {
+    MXM_ENTER();
+    int64_t n_tiles = 0;
+    RC_TRY(samples_check(c, row0_host, S, H, "mxm_votes_samples", &n_tiles));
+    if (ln_props == nullptr || best == nullptr || votes == nullptr || first == nullptr)
+        return fail(-1, "mxm_votes_samples: bad arguments (ln_props, best, votes and first are required)");
+    if (lse != nullptr && (props == nullptr || rowmax == nullptr))
+        return fail(-1, "mxm_votes_samples: lse needs props and rowmax (the row normaliser's own variables)");
+    RC_TRY(finish_ws_check("mxm_votes_samples", ws, ws_bytes, n_tiles, S, 0));
+    hipStream_t s = (hipStream_t)stream;
+    const finish_ws L = finish_layout(ws, n_tiles, (int)S, 0);
+    const size_t vlds = (size_t)H * (sizeof(double) + 2 * sizeof(int));
+    RC_TRY(dynamic_lds_ok(reinterpret_cast<const void *>(&votes_sum_samples_kernel), vlds, "votes_sum_samples_kernel",
+                          "mxm_votes_samples", H, "too wide for the vote kernel"));
+    RC_TRY(finish_upload(row0_host, (int)S, n_tiles, 0, nullptr, nullptr, nullptr, L, s));
+    const int ldc = coded_ld(H);
+    if (lse != nullptr)
+        hipLaunchKernelGGL((votes_best_samples_kernel<true>), dim3((unsigned)n_tiles), dim3(SFIN_THREADS), 0, s, c->rec, c->rec_off,
+                           c->ndist, ldc, (int)H, (const mxm_sample_tile *)L.tiles, ln_props, props, rowmax, best, lse);
+    else
+        hipLaunchKernelGGL((votes_best_samples_kernel<false>), dim3((unsigned)n_tiles), dim3(SFIN_THREADS), 0, s, c->rec, c->rec_off,
+                           c->ndist, ldc, (int)H, (const mxm_sample_tile *)L.tiles, ln_props, props, rowmax, best, lse);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(votes_sum_samples_kernel, dim3((unsigned)S), dim3(SFIN_THREADS), vlds, s, (const int32_t *)best, w,
+                       (const int64_t *)L.row0, (int)H, votes, counts, first, state);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mxm_gather_columns_samples(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H,
+                                          const int32_t *cols_host, const int32_t *ncol_host, int32_t ld, double *out, void *ws,
+                                          size_t ws_bytes, void *stream) {
+    MXM_ENTER();
+    int64_t n_tiles = 0;
+    RC_TRY(samples_check(c, row0_host, S, H, "mxm_gather_columns_samples", &n_tiles));
+    if (cols_host == nullptr || out == nullptr) return fail(-1, "mxm_gather_columns_samples: bad arguments");
+    RC_TRY(finish_cols_check("mxm_gather_columns_samples", S, H, ld, ncol_host, cols_host, nullptr));
+    RC_TRY(finish_ws_check("mxm_gather_columns_samples", ws, ws_bytes, n_tiles, S, ld));
+    hipStream_t s = (hipStream_t)stream;
+    const finish_ws L = finish_layout(ws, n_tiles, (int)S, (int)ld);
+    RC_TRY(finish_upload(row0_host, (int)S, n_tiles, (int)ld, ncol_host, cols_host, nullptr, L, s));
+    hipLaunchKernelGGL(gather_samples_kernel, dim3((unsigned)n_tiles), dim3(SFIN_THREADS), 0, s, c->rec, c->rec_off, c->ndist,
+                       coded_ld(H), (const mxm_sample_tile *)L.tiles, (const int32_t *)L.cols, (const int32_t *)L.ncol, (int)ld, out);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// LDS of em_loop_samples_narrow_kernel for the linearised sample: 72 KiB at most, so that two workgroups (each with its
+// 0.5 KiB of wave sums) still fit a CU's 160 KiB; a batch of smaller samples asks for what its largest one needs.
+#define SFIN_LDS_DOUBLES (72 * 1024 / 8)
+
+extern "C" int mxm_em_loop_samples_narrow(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, const double *M,
+                                          int32_t ld, const int32_t *ncol_host, const double *w, double *props_cur, double *ln_cur,
+                                          double *ln_new, mxm_em_state *state, double tol, int32_t max_iter, int32_t check_every,
+                                          double *E, void *ws, size_t ws_bytes, void *stream, mxm_em_state *state_host) {
+    MXM_ENTER();
+    int64_t n_tiles = 0;
+    RC_TRY(samples_check(c, row0_host, S, H, "mxm_em_loop_samples_narrow", &n_tiles));
+    if (M == nullptr || props_cur == nullptr || ln_cur == nullptr || ln_new == nullptr || state == nullptr || state_host == nullptr)
+        return fail(-1, "mxm_em_loop_samples_narrow: bad arguments");
+    RC_TRY(finish_cols_check("mxm_em_loop_samples_narrow", S, H, ld, ncol_host, nullptr, nullptr));
+    RC_TRY(finish_ws_check("mxm_em_loop_samples_narrow", ws, ws_bytes, n_tiles, S, ld));
+    // the linearised samples: in LDS where they fit, else in the global copy E
+    int64_t lds_doubles = 0;
+    bool spills = false;
+    for (int32_t b = 0; b < S; ++b) {
+        const int64_t cells = (row0_host[b + 1] - row0_host[b]) * (int64_t)ncol_host[b];
+        if (cells <= SFIN_LDS_DOUBLES) lds_doubles = std::max(lds_doubles, cells);
+        else spills = true;
+    }
+    if (spills && E == nullptr)
+        return fail(-1, "mxm_em_loop_samples_narrow: a sample of more than %d cells needs the global copy E", SFIN_LDS_DOUBLES);
+    if (check_every < 1) check_every = 1;
+    if (T.progress != nullptr && check_every > T.progress_every) check_every = T.progress_every;
+    hipStream_t s = (hipStream_t)stream;
+    const finish_ws L = finish_layout(ws, n_tiles, (int)S, (int)ld);
+    const size_t lds = (size_t)lds_doubles * sizeof(double);
+    // the opt-in to more than 64 KiB of dynamic LDS once, before the loop
+    int lds_rc = -1;
+    (void)dispatch_width<SFIN_KMAX>((int)ld, [&](auto n) {
+        constexpr int LD = decltype(n)::value;
+        if constexpr (LD == 4 || LD == 8 || LD == 16)
+            lds_rc = dynamic_lds_ok(reinterpret_cast<const void *>(&em_loop_samples_narrow_kernel<LD>), lds, "em_loop_samples_narrow_kernel");
+    });
+    RC_TRY(lds_rc);
+    auto launch = [&](int chunk) -> int {
+        bool launched = false;
+        (void)dispatch_width<SFIN_KMAX>((int)ld, [&](auto n) {
+            constexpr int LD = decltype(n)::value;
+            if constexpr (LD == 4 || LD == 8 || LD == 16) {
+                hipLaunchKernelGGL((em_loop_samples_narrow_kernel<LD>), dim3((unsigned)S), dim3(SFIN_THREADS), lds, s, M, E, w,
+                                   (const int64_t *)L.row0, (const int32_t *)L.ncol, ln_cur, ln_new, props_cur, state, tol,
+                                   (int)max_iter, chunk, (int)lds_doubles);
+                launched = true;
+            }
+        });
+        if (!launched) return fail(-1, "mxm_em_loop_samples_narrow: ld = %d has no kernel instance", ld);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    RC_TRY(finish_upload(row0_host, (int)S, n_tiles, (int)ld, ncol_host, nullptr, nullptr, L, s));
+    RC_TRY(read_state(state_host, state, S, s));
+    auto running = [&]() {
+        int n = 0;
+        for (int b = 0; b < S; ++b) n += (state_host[b].done == 0 && ncol_host[b] > 0) ? 1 : 0;
+        return n;
+    };
+    while (max_iter > 0 && running() > 0) {
+        RC_TRY(launch((int)check_every));
+        RC_TRY(read_state(state_host, state, S, s));
+        if (T.progress != nullptr) T.progress(state_host, S, T.progress_user);
+    }
+    return 0;
+}
+
+extern "C" int mxm_assign_reads_samples(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, const double *M,
+                                        int32_t ld, const int32_t *ncol_host, const int32_t *perm_host, const double *ln_theta,
+                                        const double *props, const double *log_props, const double *lse, double log_min_fold,
+                                        int32_t *assigned, double *post, void *ws, size_t ws_bytes, void *stream) {
+    MXM_ENTER();
+    int64_t n_tiles = 0;
+    RC_TRY(samples_check(c, row0_host, S, H, "mxm_assign_reads_samples", &n_tiles));
+    if (M == nullptr || perm_host == nullptr || ln_theta == nullptr || props == nullptr || log_props == nullptr || assigned == nullptr)
+        return fail(-1, "mxm_assign_reads_samples: bad arguments");
+    RC_TRY(finish_cols_check("mxm_assign_reads_samples", S, H, ld, ncol_host, nullptr, perm_host));
+    RC_TRY(finish_ws_check("mxm_assign_reads_samples", ws, ws_bytes, n_tiles, S, ld));
+    hipStream_t s = (hipStream_t)stream;
+    const finish_ws L = finish_layout(ws, n_tiles, (int)S, (int)ld);
+    RC_TRY(finish_upload(row0_host, (int)S, n_tiles, (int)ld, ncol_host, nullptr, perm_host, L, s));
+    bool launched = false;
+    (void)dispatch_width<SFIN_KMAX>((int)ld, [&](auto n) {
+        constexpr int LD = decltype(n)::value;
+        if constexpr (LD == 4 || LD == 8 || LD == 16) {
+            hipLaunchKernelGGL((assign_samples_kernel<LD>), dim3((unsigned)n_tiles), dim3(64), 0, s, M, (const mxm_sample_tile *)L.tiles,
+                               (const int32_t *)L.ncol, (const int32_t *)L.perm, ln_theta, props, log_props, lse, log_min_fold,
+                               assigned, post);
+            launched = true;
+        }
+    });
+    if (!launched) return fail(-1, "mxm_assign_reads_samples: ld = %d has no kernel instance", ld);
+    HIP_TRY(hipGetLastError());
     return 0;
 }
 

@@ -825,6 +825,116 @@ class SampleBatch(object):
         return ln_cur, ln_new, [(s.done, s.iters, s.l1) for s in host_state]
 
 
+class SampleFinish(object):
+    """
+    The second half of a cohort run over the rows of many samples back to back in ONE records matrix, as SampleBatch holds
+    them (assign.finish_many drives it): the contributor vote (mxm_votes_samples), the column gather
+    (mxm_gather_columns_samples), the refinement loop with ONE workgroup per sample (mxm_em_loop_samples_narrow) and the
+    read assignment (mxm_assign_reads_samples).  rowmax [R]: the records' row maxima (CodedMatrix.rowmax), for the row
+    normaliser of the unrefined assignment.  Every per-sample table is [S][ld] with ld = 4, 8 or 16.
+    """
+    KMAX = 16
+
+    def __init__(self, rec, rec_off, ndist, wts, rowmax, row0, n_haps):
+        self.lib = _lib.load()
+        self.dev = rec.device
+        self.rec, self.rec_off, self.ndist, self.wts = rec, rec_off.contiguous(), ndist.contiguous(), wts.contiguous()
+        self.rowmax = None if rowmax is None else rowmax.contiguous()
+        self.row0 = numpy.ascontiguousarray(row0, dtype=numpy.int64)
+        self.n_entries, self.n_rows, self.n_haps = len(self.row0) - 1, int(self.row0[-1]), int(n_haps)
+        if self.rec_off.numel() != self.n_rows or self.ndist.numel() != self.n_rows or self.wts.numel() != self.n_rows:
+            raise ValueError("rec_off / ndist / weights do not match row0")
+        self.coded = _lib.Coded(self.rec.data_ptr(), self.rec_off.data_ptr(), self.ndist.data_ptr(), self.n_rows,
+                                None, 0, None, 0, None, 0)
+        self.row0_ptr = self.row0.ctypes.data_as(ctypes.c_void_p)
+        self.n_tiles = int(self.lib.mxm_samples_plan(self.row0_ptr, self.n_entries, None, 0, None))
+        if self.n_tiles < 0:
+            raise ValueError("mxm_samples_plan failed: %s" % self.lib.mxm_last_error().decode("utf-8", "replace"))
+        self.ws_bytes = int(self.lib.mxm_samples_finish_workspace_bytes(self.n_tiles, self.n_entries, self.KMAX))
+        self.ws = torch.empty(self.ws_bytes // 8 + 2, dtype=torch.float64, device=self.dev)
+
+    @staticmethod
+    def _i32(table):
+        arr = numpy.ascontiguousarray(table, dtype=numpy.int32)
+        return arr, arr.ctypes.data_as(ctypes.c_void_p)
+
+    def votes(self, ln_props, want_lse=False):
+        """ln_props [S][H] (host).  Returns (best int32[R] device, votes [S][H], counts [S][H], first [S][H] on the host,
+        lse [R] device or None, error flags [S])."""
+        n, n_haps = self.n_entries, self.n_haps
+        host = numpy.ascontiguousarray(ln_props, dtype=numpy.float64)
+        if host.shape != (n, n_haps):
+            raise ValueError("ln_props must be [%d][%d]" % (n, n_haps))
+        lnp = torch.from_numpy(host).to(self.dev)
+        props = torch.from_numpy(numpy.exp(host)).to(self.dev) if want_lse else None
+        if want_lse and self.rowmax is None:
+            raise ValueError("the row normaliser needs the records' rowmax")
+        best = torch.empty(self.n_rows, dtype=torch.int32, device=self.dev)
+        votes = torch.empty((n, n_haps), dtype=torch.float64, device=self.dev)
+        table = torch.empty((2, n, n_haps), dtype=torch.int64, device=self.dev)      # counts, first-seen rows
+        lse = torch.empty(self.n_rows, dtype=torch.float64, device=self.dev) if want_lse else None
+        state = new_state(n, self.dev)
+        _lib.check(self.lib.mxm_votes_samples(ctypes.byref(self.coded), self.row0_ptr, n, n_haps, self.wts.data_ptr(),
+                                              lnp.data_ptr(), ptr(props), ptr(self.rowmax) if want_lse else None,
+                                              best.data_ptr(), votes.data_ptr(), table[0].data_ptr(), table[1].data_ptr(),
+                                              ptr(lse), state.data_ptr(), self.ws.data_ptr(), self.ws_bytes, current_stream()),
+                   "mxm_votes_samples")
+        raw = state.cpu().numpy().tobytes()
+        errors = [st.error != 0 for st in (_lib.EmState * n).from_buffer_copy(raw)]
+        table_h = table.cpu().numpy()
+        return best, votes.cpu().numpy(), table_h[0], table_h[1], lse, errors
+
+    def gather(self, cols, ncol, ld):
+        """out[r][i] = M[r][cols[s][i]] (i < ncol[s]; -inf in the pad columns): [R][ld] on the device."""
+        cols_h, cols_p = self._i32(cols)
+        ncol_h, ncol_p = self._i32(ncol)
+        out = device_empty((self.n_rows, ld), torch.float64, self.dev, "the reduced EM matrices")
+        _lib.check(self.lib.mxm_gather_columns_samples(ctypes.byref(self.coded), self.row0_ptr, self.n_entries, self.n_haps,
+                                                       cols_p, ncol_p, ld, out.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
+                                                       current_stream()), "mxm_gather_columns_samples")
+        return out
+
+    def em_loop(self, mat, ld, ncol, inits, tolerance, max_iter, check_every=16):
+        """em_loop for every sample's reduced matrix at once, one workgroup per sample: inits[s] = [ncol[s]] linear.
+        Returns (ln_cur, ln_new) as [S][ld] numpy arrays and [(done, iters, l1)]."""
+        n = self.n_entries
+        ncol_h, ncol_p = self._i32(ncol)
+        p0 = numpy.zeros((n, ld), dtype=numpy.float64)
+        for s in range(n):
+            p0[s, :ncol_h[s]] = numpy.asarray(inits[s], dtype=numpy.float64).reshape(-1)
+        ln0, p0 = log_inits(p0)
+        props_cur = torch.from_numpy(p0).to(self.dev)
+        ln_cur = torch.from_numpy(ln0).to(self.dev)
+        ln_new = ln_cur.clone()
+        state = new_state(n, self.dev)
+        host_state = (_lib.EmState * n)()
+        lin = device_empty((self.n_rows, ld), torch.float64, self.dev, "the linearised reduced matrices")
+        _lib.check(self.lib.mxm_em_loop_samples_narrow(ctypes.byref(self.coded), self.row0_ptr, n, self.n_haps, mat.data_ptr(),
+                                                       ld, ncol_p, self.wts.data_ptr(), props_cur.data_ptr(), ln_cur.data_ptr(),
+                                                       ln_new.data_ptr(), state.data_ptr(), float(tolerance), int(max_iter),
+                                                       int(check_every), lin.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
+                                                       current_stream(), host_state), "mxm_em_loop_samples_narrow")
+        return ln_cur.cpu().numpy(), ln_new.cpu().numpy(), [(s.done, s.iters, s.l1) for s in host_state]
+
+    def assign(self, mat, ld, ncol, perm, ln_theta, log_props, lse, min_fold, want_post=False):
+        """assigned int32[R] (device; contributor ordinal or -1) and, on request, the reduced posterior [R][ld]."""
+        n = self.n_entries
+        ncol_h, ncol_p = self._i32(ncol)
+        perm_h, perm_p = self._i32(perm)
+        ln_h = numpy.ascontiguousarray(ln_theta, dtype=numpy.float64)
+        ln_d = torch.from_numpy(ln_h).to(self.dev)
+        props_d = torch.from_numpy(numpy.exp(ln_h)).to(self.dev)
+        lp_d = torch.from_numpy(numpy.ascontiguousarray(log_props, dtype=numpy.float64)).to(self.dev)
+        assigned = torch.empty(self.n_rows, dtype=torch.int32, device=self.dev)
+        post = device_empty((self.n_rows, ld), torch.float64, self.dev, "the reduced posteriors") if want_post else None
+        _lib.check(self.lib.mxm_assign_reads_samples(ctypes.byref(self.coded), self.row0_ptr, n, self.n_haps, mat.data_ptr(), ld,
+                                                     ncol_p, perm_p, ln_d.data_ptr(), props_d.data_ptr(), lp_d.data_ptr(),
+                                                     ptr(lse), float(numpy.log(min_fold)), assigned.data_ptr(), ptr(post),
+                                                     self.ws.data_ptr(), self.ws_bytes, current_stream()),
+                   "mxm_assign_reads_samples")
+        return assigned, post
+
+
 def _fold_runs(ln_next):
     """collect_result's proportions: exp(mean of the runs' LOG proportions), in run order (em.py:155, :163)."""
     res = ln_next[0].copy()
@@ -862,7 +972,8 @@ def run_em_many(samples, args, inits=None, tables=None):
     inits: None = drawn as run_em draws them, from numpy's global legacy stream, sample after sample (n_multi draws
     each): sample s alone at the same position of the stream reproduces its own draw; or a list with inits[s] [H] or
     [n_multi][H].
-    Not here: the posterior matrix, votes, contributors (per sample: run_em_ex(records=...) / assign), the quad
+    The second half -- votes, contributors, refinement and read assignment of every sample -- is assign.finish_many
+    over these results, batched likewise.  Not here: the posterior matrix (per sample: run_em_ex(records=...)), the quad
     dictionary, several GPUs, fp32 storage.
     """
     from . import preprocess
