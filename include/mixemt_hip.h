@@ -746,4 +746,6 @@ void mxm_exchange_destroy(mxm_exchange *x);
 }
 #endif
 #include "mixemt_hip_samples_finish.h"
+/* mixemt's variant check for the samples of a cohort, over pileups that stay on the device */
+#include "mixemt_hip_var_check.h"
 #endif /* MIXEMT_HIP_H */

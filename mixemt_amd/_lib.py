@@ -199,6 +199,13 @@ FINISH_SIGNATURES = {
                                                 c_ptr, c_ptr, c_ptr, c_ptr, c_f64, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
 }
 
+# the variant check of a cohort's samples over pileups on the device (include/mixemt_hip_var_check.h: an addition behind ABI
+# version 603); its refusals are pinned in tests/test_var_check_host.py
+VARCHECK_SIGNATURES = {
+    "mxm_check_variants_samples": (ctypes.c_int, [c_ptr, c_i32, c_i64, c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_i32, c_i64, c_ptr,
+                                                  c_ptr, c_i32, c_f64, c_f64, c_f64, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
+}
+
 # the MXM_VERSION of include/mixemt_hip.h these signatures were written for; load() refuses any other
 ABI_VERSION = 603
 
@@ -235,7 +242,8 @@ def load():
     if have != ABI_VERSION:
         raise MixemtHipError("%s reports ABI version %s, this binding was written for %d: rebuild with "
                              "`python -m mixemt_amd.build --force`" % (LIB_PATH, have, ABI_VERSION))
-    for name, (restype, argtypes) in list(SIGNATURES.items()) + list(FINISH_SIGNATURES.items()):
+    for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(FINISH_SIGNATURES.items())
+                                      + list(VARCHECK_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -158,6 +158,93 @@ class AlignmentColumns(object):
         return cols, keep
 
 
+def concat_columns(cols_list):
+    """
+    The AlignmentColumns of many samples back to back, for one upload and one labelled pileup call
+    (observe.observe_bases_many): -> (AlignmentColumns, aln0) with aln0 int64 [S + 1], sample s owning the alignments
+    [aln0[s], aln0[s + 1]).  cig_ptr / seq_ptr are re-based; frag is re-based so that fragments of different samples never
+    share an index, and names are concatenated in that order; is_reverse / qual / has_qual are kept -- absent in some
+    samples and present in others: zeros (forward; no qualities) for the samples without.  Samples without alignments
+    are allowed; an empty list is a ValueError.
+    """
+    cols_list = list(cols_list)
+    if not cols_list:
+        raise ValueError("concat_columns: no samples")
+    n_aln = [len(c) for c in cols_list]
+    aln0 = numpy.zeros(len(cols_list) + 1, dtype=numpy.int64)
+    numpy.cumsum(n_aln, out=aln0[1:])
+
+    def offsets(name, data):
+        parts, base = [numpy.zeros(1, dtype=numpy.int64)], 0
+        for c in cols_list:
+            ptr = getattr(c, name)
+            parts.append(ptr[1:] + base)
+            base += int(ptr[-1])
+        body = [getattr(c, data)[:int(getattr(c, name)[-1])] for c in cols_list]
+        return numpy.concatenate(parts), body
+
+    cig_ptr, cigar = offsets("cig_ptr", "cigar")
+    seq_ptr, seq = offsets("seq_ptr", "seq")
+    frags, name_parts, base = [], [], 0
+    for c in cols_list:
+        n_frag = max(len(c.names), int(c.frag.max()) + 1 if len(c) else 0)
+        frags.append(c.frag + base)
+        name_parts.append((c.names, n_frag))
+        base += n_frag
+
+    # qual and has_qual together, sample by sample.  A sample without qualities gets zeros in both; one with qualities
+    # but no has_qual column ("every alignment has them") gets ones.  Neither column is made when no sample has qualities,
+    # and has_qual stays absent when every sample has qualities and none has the column.
+    any_qual = any(c.qual is not None for c in cols_list)
+    need_has = any_qual and any(c.qual is None or c.has_qual is not None for c in cols_list)
+    quals, has_quals, strands = [], [], []
+    any_strand = any(c.is_reverse is not None for c in cols_list)
+    for c, n in zip(cols_list, n_aln):
+        n_seq = int(c.seq_ptr[-1])
+        if any_qual:
+            quals.append(numpy.zeros(n_seq, dtype=numpy.uint8) if c.qual is None else c.qual[:n_seq])
+        if need_has:
+            if c.qual is None:
+                has_quals.append(numpy.zeros(n, dtype=numpy.uint8))
+            else:
+                has_quals.append(numpy.ones(n, dtype=numpy.uint8) if c.has_qual is None else c.has_qual)
+        if any_strand:
+            strands.append(numpy.zeros(n, dtype=numpy.uint8) if c.is_reverse is None else c.is_reverse)
+    out = AlignmentColumns(numpy.concatenate([c.ref_start for c in cols_list]), numpy.concatenate([c.mapq for c in cols_list]),
+                           numpy.concatenate(frags), cig_ptr, numpy.concatenate(cigar), seq_ptr, numpy.concatenate(seq),
+                           numpy.concatenate(quals) if any_qual else None, numpy.concatenate(has_quals) if need_has else None,
+                           ConcatNames(name_parts), numpy.concatenate(strands) if any_strand else None)
+    return out, aln0
+
+
+class ConcatNames(object):
+    """The fragment names of concat_columns: the samples' own name sequences one after another, looked up (and, for a
+    FragmentNames, decoded) only when asked for -- the pileup never needs them.  parts: (names, n_frag) per sample; an
+    index past a sample's own names (a fragment index without a name) gives ''."""
+
+    def __init__(self, parts):
+        self._parts = [names for names, _ in parts]
+        self._start = numpy.concatenate([[0], numpy.cumsum([n for _, n in parts])]).astype(numpy.int64)
+
+    def __len__(self):
+        return int(self._start[-1])
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return [self[k] for k in range(*i.indices(len(self)))]
+        i = int(i)
+        if i < 0:
+            i += len(self)
+        if not 0 <= i < len(self):
+            raise IndexError("fragment index out of range")
+        s = int(numpy.searchsorted(self._start, i, side="right")) - 1
+        own, k = self._parts[s], i - int(self._start[s])
+        return own[k] if k < len(own) else ""
+
+    def __iter__(self):
+        return (self[i] for i in range(len(self)))
+
+
 class FragmentNames(object):
     """The fragments' read names as one byte string + offsets (read_bam): a sequence of str, decoded when looked at."""
 

@@ -9,6 +9,8 @@ reference's NumPy versions would need:
     get_contributors (+ _records) <- assemble.get_contributors        assemble.py:31-100
     check_contrib_phy_vars     <- assemble._check_contrib_phy_vars    assemble.py:126-208 (host logic over the pileup of
                                   observe.observe_bases)
+    check_variants_samples     <- the same for the samples of a cohort in one launch, over pileups on the device
+                                  (VarCheckTables: the tree's variants as arrays; finish_many(obs=CohortPileup))
     read_votes / report_read_votes <- stats.report_read_votes          stats.py:34-45
     update_contribs            <- assemble.update_contribs             assemble.py:211-230
     assign_read_indexes        <- assemble.assign_read_indexes         assemble.py:284-334
@@ -212,6 +214,11 @@ def _contributor_table(phylo, obs, haplogroups, props, find, args):
     contrib_prop.sort(key=lambda con: con[1], reverse=True)
     if args.var_check and not getattr(args, "contributors", None):
         contrib_prop = check_contrib_phy_vars(phylo, obs, contrib_prop, args)
+    return _name_contributors(contrib_prop)
+
+
+def _name_contributors(contrib_prop):
+    """[[haplogroup, proportion], ...] -> [[hapNN, haplogroup, proportion], ...] (assemble.py:93-99)."""
     name_fmt = "hap%%0%dd" % (len(str(len(contrib_prop) + 1)))
     for num, con in enumerate(contrib_prop):
         con.insert(0, name_fmt % (num + 1))
@@ -504,6 +511,116 @@ def assign_reads(cols, contribs, em_results, haps, reads, args, dcols=None):
     return ContribReads(cols, labels, names, list(table), dcols, frag_d)
 
 
+# ---- the variant check of many samples on the device (mxm_check_variants_samples) ------------------------------------------
+VAR_CHECK_MAX_CANDS = 64            # candidates a sample may have on the device route (the widest table stride of the entry)
+VAR_CHECK_MAX_L = 131072            # MXM_VAR_CHECK_MAX_L of include/mixemt_hip_var_check.h: the kernel's bitsets live in LDS
+
+
+class VarCheckTables(object):
+    """
+    What check_contrib_phy_vars reads from the tree, as int32 arrays in the column order of `haplogroups` (numpy: the
+    attributes ending in _h; device tensors without the suffix when a device was given):
+        key_ptr [H + 1], key [nnz]   the keys of haplogroup h are the distinct pos * 4 + code of (pos_from_var(v),
+                                     der_allele(v)) for v in phylo.hap_var[h], code = index in "ACGT", ascending
+        site [n_sites]               phylo.get_variant_pos(), ascending
+        site_key [n_sites]           site * 4 + code of refseq[site], or -1 where the reference base is not one of ACGT
+        max_pos                      the largest position in key / site (-1: none); n_haps; phylo: the tree it was built from
+    The tables are built from hap_var / variants as they stand when build() is called, so custom haplogroups
+    (add_custom_hap) and ignored sites (ignore_sites) are covered -- and a tree edited afterwards needs a new build.
+    """
+    CODES = {base: code for code, base in enumerate("ACGT")}
+
+    def __init__(self, phylo, key_ptr, key, site, site_key, dev=None):
+        self.phylo = phylo
+        self.key_ptr_h, self.key_h, self.site_h, self.site_key_h = key_ptr, key, site, site_key
+        self.n_haps = len(key_ptr) - 1
+        self.max_pos = max(int(key.max()) >> 2 if len(key) else -1, int(site.max()) if len(site) else -1)
+        self.device = dev
+        self.key_ptr = self.key = self.site = self.site_key = None
+        if dev is not None:
+            def up(arr):
+                return torch.from_numpy(arr if arr.size else numpy.zeros(1, dtype=numpy.int32)).to(dev)
+            self.key_ptr, self.key, self.site, self.site_key = up(key_ptr), up(key), up(site), up(site_key)
+
+    @classmethod
+    def build(cls, phylo, haplogroups, dev=None):
+        """The tables of `phylo` for the columns `haplogroups` (uploaded to `dev` when given), or None when a derived
+        allele is not one of ACGT: the caller then takes the host route."""
+        from .phylotree import der_allele, pos_from_var
+        codes = cls.CODES
+        seen = {}                                             # variant string -> key (the haplogroups share most of them)
+        key_ptr = numpy.zeros(len(haplogroups) + 1, dtype=numpy.int64)
+        keys = []
+        for h, hap in enumerate(haplogroups):
+            own = set()
+            for var in phylo.hap_var[hap]:
+                k = seen.get(var)
+                if k is None:
+                    code = codes.get(der_allele(var))
+                    if code is None:
+                        return None
+                    k = seen[var] = pos_from_var(var) * 4 + code
+                own.add(k)
+            keys.extend(sorted(own))
+            key_ptr[h + 1] = len(keys)
+        site = numpy.asarray(phylo.get_variant_pos(), dtype=numpy.int64)
+        # A reference base outside ACGT (say 'N') gives -1 and is never claimed: the claimed pairs are only ever compared
+        # with (position, derived base) pairs, whose base IS one of ACGT, so a claimed (pos, 'N') can never equal one and
+        # dropping it changes no decision.
+        ref_code = [codes.get(phylo.refseq[p]) for p in site.tolist()]
+        site_key = numpy.array([-1 if code is None else p * 4 + code for p, code in zip(site.tolist(), ref_code)],
+                               dtype=numpy.int64)
+        if (len(keys) and max(keys) >= 2 ** 31) or len(keys) >= 2 ** 31:
+            return None
+        return cls(phylo, key_ptr.astype(numpy.int32), numpy.asarray(keys, dtype=numpy.int32).reshape(-1),
+                   site.astype(numpy.int32), site_key.astype(numpy.int32), dev)
+
+
+def _var_check_ld(widest):
+    for ld in (4, 8, 16, 32, 64):
+        if widest <= ld:
+            return ld
+    raise ValueError("the device variant check takes at most %d candidates per sample" % VAR_CHECK_MAX_CANDS)
+
+
+def check_variants_samples(counts, tables, cands, args, want_counts=False):
+    """
+    check_contrib_phy_vars for many samples in ONE launch (mxm_check_variants_samples) over pileups on the device.
+    counts: int32 device tensor [S][L][16] (observe.CohortPileup.counts); tables: a VarCheckTables built with a device;
+    cands: per sample the candidates' haplogroup indexes in checking order (descending proportion); args: min_var_reads,
+    frac_var_reads, var_fraction, var_count.  Returns keep (numpy bool [S][ld]: keep[s][:len(cands[s])] is the sample's)
+    and, with want_counts, also n_uniq and n_found (int32 [S][ld]): the two numbers the reference prints per candidate.
+    """
+    if counts.dim() != 3 or counts.shape[2] != 16 or counts.dtype != torch.int32 or not counts.is_contiguous():
+        raise ValueError("counts must be a contiguous int32 [S][L][16] device tensor")
+    if tables.key_ptr is None:
+        raise ValueError("check_variants_samples: the tables were built without a device")
+    n = len(cands)
+    if counts.shape[0] != n:
+        raise ValueError("check_variants_samples: %d pileups for %d candidate lists" % (counts.shape[0], n))
+    ld = _var_check_ld(max([len(c) for c in cands] + [1]))
+    cand = numpy.zeros((n, ld), dtype=numpy.int32)
+    ncand = numpy.zeros(n, dtype=numpy.int32)
+    for s, c in enumerate(cands):
+        ncand[s] = len(c)
+        cand[s, :len(c)] = c
+    dev = counts.device
+    keep = torch.zeros((n, ld), dtype=torch.uint8, device=dev)
+    n_uniq = torch.zeros((n, ld), dtype=torch.int32, device=dev) if want_counts else None
+    n_found = torch.zeros((n, ld), dtype=torch.int32, device=dev) if want_counts else None
+    var_count = getattr(args, "var_count", None)
+    _lib.check(_lib.load().mxm_check_variants_samples(
+        counts.data_ptr(), n, int(counts.shape[1]), tables.key_ptr.data_ptr(), tables.key.data_ptr(), tables.n_haps,
+        tables.site.data_ptr(), tables.site_key.data_ptr(), len(tables.site_h), tables.max_pos, cand.ctypes.data,
+        ncand.ctypes.data, ld, float(args.min_var_reads), float(args.frac_var_reads), float(args.var_fraction),
+        0 if var_count is None else 1, 0 if var_count is None else int(var_count), keep.data_ptr(), ptr(n_uniq), ptr(n_found),
+        current_stream()), "mxm_check_variants_samples")
+    keep_h = keep.cpu().numpy().astype(bool)
+    if want_counts:
+        return keep_h, n_uniq.cpu().numpy(), n_found.cpu().numpy()
+    return keep_h
+
+
 # ---- the second half of a cohort run, batched (em.run_em_many's counterpart) ------------------------------------------
 FINISH_KMAX = 16                    # contributors a batched sample may have (the reduced matrix's widest row stride)
 FINISH_MAX_ROWS = 100000            # rows up to which one workgroup per sample was measured not slower than the per-sample
@@ -585,7 +702,7 @@ def _fixed_contributors(args, hap_index):
     return cols
 
 
-def _finish_check(samples, results, haplogroups, args, obs):
+def _finish_check(samples, results, haplogroups, args, obs, phylo=None, var_tables=None):
     """finish_many's argument checks (host only); returns the haplogroup -> index table."""
     from .preprocess import CodedMatrix
     if not samples or len(results) != len(samples):
@@ -607,13 +724,24 @@ def _finish_check(samples, results, haplogroups, args, obs):
                              "per sample) and phylo=")
         if len(obs) != len(samples):
             raise ValueError("finish_many: obs needs one entry per sample (%d samples, %d entries)" % (len(samples), len(obs)))
+        if _is_cohort_pileup(obs):
+            if phylo is None:
+                raise ValueError("finish_many: the variant check needs phylo=")
+            if var_tables is not None and var_tables.n_haps != len(haplogroups):
+                raise ValueError("finish_many: var_tables was built for %d haplogroups, the samples have %d"
+                                 % (var_tables.n_haps, len(haplogroups)))
     return hap_index, fixed
+
+
+def _is_cohort_pileup(obs):
+    from .observe import CohortPileup
+    return isinstance(obs, CohortPileup)
 
 
 def _empty_finish(route, order, votes):
     return {"contribs": [], "vote_order": order, "votes": votes, "sub_haps": [], "refined": None,
             "assigned": AssignedReads(numpy.zeros(0, dtype=numpy.int32), []), "row_label": numpy.zeros(0, dtype=numpy.int32),
-            "route": route, "posterior": None}
+            "route": route, "posterior": None, "var_check": None}
 
 
 def _finish_single(cm, wts, res, contribs, order, votes, haplogroups, hap_index, args, init, want_posterior):
@@ -636,7 +764,7 @@ def _finish_single(cm, wts, res, contribs, order, votes, haplogroups, hap_index,
         table, assigned = _assign_rows(contribs, (res["props"], read_mix), haplogroups, cm.n_rows, args.min_fold)
     label = numpy.zeros(cm.n_rows, dtype=numpy.int32) if assigned is None else assigned.cpu().numpy()
     return {"contribs": contribs, "vote_order": order, "votes": votes, "sub_haps": sub_haps, "refined": refined,
-            "assigned": table, "row_label": label, "route": "single", "posterior": posterior}
+            "assigned": table, "row_label": label, "route": "single", "posterior": posterior, "var_check": None}
 
 
 def _finish_batch(samples, wts_d, ids):
@@ -649,7 +777,7 @@ def _finish_batch(samples, wts_d, ids):
 
 
 def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refine_inits=None, max_rows=None,
-                want_posterior=False):
+                want_posterior=False, var_tables=None):
     """
     What mixemt reports for a sample after its EM (bin/mixemt:298-323: get_contributors, the refinement run_em on the
     contributors' columns with update_contribs, assign_read_indexes) for ALL samples of one em.run_em_many call in
@@ -660,8 +788,15 @@ def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refin
     results: run_em_many's list (props and ln_theta_k are read).
     args: the reference's namespace -- min_reads, contributors, var_check (with min_var_reads, frac_var_reads, var_count,
         var_fraction, verbose), refine_ests, min_fold, tolerance, max_iter, init_alpha, n_multi.
-    phylo / obs: for the variant check (check_contrib_phy_vars, run per sample on the host as it is): obs is a list with
-        one observe.ObservedBases per sample, required when args.var_check is set and args.contributors is empty.
+    phylo / obs: for the variant check, required when args.var_check is set and args.contributors is empty.  obs is a list
+        with one observe.ObservedBases per sample (check_contrib_phy_vars, run per sample on the host as it is), or an
+        observe.CohortPileup (observe.observe_bases_many): the pileups stay on the device and ONE
+        mxm_check_variants_samples call checks every sample with at most 64 candidates (a sample on the "single" route
+        after its own vote); what that call cannot take goes through check_contrib_phy_vars over obs.host(s), unchanged --
+        args.verbose (the stderr lines are the reference's), a sample with more candidates, a tree with a derived allele
+        outside ACGT, a pileup shorter than the tree's last variant or longer than 131 072 positions.
+    var_tables: a VarCheckTables.build(phylo, haplogroups, device) to reuse between calls (CohortPileup only); built once per
+        call otherwise.  A tree edited since needs a new build.
     refine_inits: None draws init_props(K_s) from numpy's global legacy stream, sample after sample, only for the samples
         that are refined -- NOT the stream position a Python loop over whole samples would reach (there the first EM's
         draw of sample s + 1 follows the refinement draw of sample s); or a list with [K_s] proportions per sample (None
@@ -679,13 +814,15 @@ def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refin
         route       "batch", or "single": the sample went through the per-sample functions -- its first EM ran on its
                     own, args.n_multi > 1 (the fold of several runs' posteriors, em.py:156, stays with the per-sample
                     path), more than max_rows rows, or more than 16 contributors
+        var_check   "device" or "host": where the sample's candidates were checked; None when the check is off
+                    (args.var_check false, or args.contributors given)
         posterior   always present; None unless want_posterior is set (an addition to mixemt's own outputs, for tests and
                     for `-s`-like dumps): then the reduced posterior under theta_k ([R_s][K_s], device), refined samples only
     A sample without a contributor returns contribs == [], refined None and an empty AssignedReads; nothing is launched
     for it.  A sample with ONE contributor is still refined on R x 1, as bin/mixemt:311-320 does.
     """
     from . import em
-    hap_index, fixed = _finish_check(samples, results, haplogroups, args, obs)
+    hap_index, fixed = _finish_check(samples, results, haplogroups, args, obs, phylo, var_tables)
     n = len(samples)
     n_multi = int(getattr(args, "n_multi", 1))
     max_rows = FINISH_MAX_ROWS if max_rows is None else int(max_rows)
@@ -695,7 +832,19 @@ def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refin
         raise ValueError("finish_many: weights do not match the samples' rows")
     route = [_finish_route(samples[s][0].n_rows, results[s].get("route"), n_multi, max_rows) for s in range(n)]
     contribs, orders, counts = [None] * n, [None] * n, [None] * n
-    obs_of = (lambda s: obs[s]) if obs is not None else (lambda s: None)
+    checked = bool(args.var_check) and fixed is None
+    cohort = checked and _is_cohort_pileup(obs)
+    if cohort:
+        obs_of = obs.host                                   # (downloads the sample's table: host-route samples only)
+    else:
+        obs_of = (lambda s: obs[s]) if obs is not None else (lambda s: None)
+    var_route = ["host" if checked else None] * n
+    on_device = False
+    if cohort and not args.verbose and obs.L <= VAR_CHECK_MAX_L:
+        if var_tables is None:
+            var_tables = VarCheckTables.build(phylo, haplogroups, dev)
+        on_device = var_tables is not None and var_tables.key_ptr is not None and var_tables.max_pos < obs.L
+    pending = {}                                            # sample -> its candidates in checking order (device route)
 
     # ---- votes and contributor tables ----
     voted = [s for s in range(n) if route[s] == "batch"]
@@ -712,13 +861,31 @@ def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refin
             order = seen[numpy.argsort(first_h[j][seen], kind="stable")]
             orders[s], counts[s] = order, counts_h[j].astype(numpy.float64)
             found = [int(h) for h in order if votes_w[j][h] >= args.min_reads]
-            contribs[s] = _contributor_table(phylo, obs_of(s), haplogroups, results[s]["props"], lambda: found, args)
+            if on_device and len(found) <= VAR_CHECK_MAX_CANDS:
+                props = results[s]["props"]
+                pending[s] = sorted(found, key=lambda con: props[con], reverse=True)    # (stable, as _contributor_table's sort)
+            else:
+                contribs[s] = _contributor_table(phylo, obs_of(s) if checked else None, haplogroups, results[s]["props"],
+                                                 lambda: found, args)
     for s in range(n):
         if route[s] == "single":
             cm = samples[s][0]
-            contribs[s] = get_contributors_records(phylo, obs_of(s), haplogroups, wts_d[s], results[s]["props"], cm,
-                                                   results[s]["ln_theta_k"], args)
             orders[s], counts[s] = vote_table_from_records(cm, results[s]["ln_theta_k"], None)
+            if on_device:                                   # (its own vote, then the cohort's one check launch)
+                found = find_contribs_from_records(cm, results[s]["ln_theta_k"], wts_d[s], args)
+                if len(found) <= VAR_CHECK_MAX_CANDS:
+                    props = results[s]["props"]
+                    pending[s] = sorted(found, key=lambda con: props[con], reverse=True)
+                    continue
+            contribs[s] = get_contributors_records(phylo, obs_of(s) if checked else None, haplogroups, wts_d[s],
+                                                   results[s]["props"], cm, results[s]["ln_theta_k"], args)
+    if pending:
+        # one launch for every sample that takes the device check; a sample that is not in it has no candidates there
+        keep = check_variants_samples(obs.counts, var_tables, [pending.get(s, []) for s in range(n)], args)
+        for s, cand in pending.items():
+            props = results[s]["props"]
+            contribs[s] = _name_contributors([[haplogroups[con], props[con]] for i, con in enumerate(cand) if keep[s, i]])
+            var_route[s] = "device"
 
     # ---- column plans; the samples that leave the batch now that their contributors are known ----
     plans = [None] * n
@@ -739,6 +906,9 @@ def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refin
         elif route[s] == "single":
             out[s] = _finish_single(samples[s][0], wts_d[s], results[s], contribs[s], orders[s], counts[s], haplogroups,
                                     hap_index, args, inits[s], want_posterior)
+    for s in range(n):
+        if out[s] is not None:
+            out[s]["var_check"] = var_route[s]
     ids = [s for s in range(n) if out[s] is None]
     if not ids:
         return out
@@ -784,6 +954,6 @@ def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refin
         label = labels[lo:hi].copy()
         out[s] = {"contribs": contribs[s], "vote_order": orders[s], "votes": counts[s], "sub_haps": plans[s][2],
                   "refined": refined[j], "assigned": AssignedReads(label, names),
-                  "row_label": label, "route": "batch",
+                  "row_label": label, "route": "batch", "var_check": var_route[s],
                   "posterior": post[lo:hi, :int(ncol[j])] if post is not None else None}
     return out

@@ -33,6 +33,7 @@
 //                       one sample's rows per workgroup)
 //   aln_encode.hpp      HOST code: mxm_aln_encode, the batched alignment front end (process_reads + reduce_reads + row order)
 //   observe_kernels.hpp observe_bucket_kernel, observe_count_kernel (the pileup of the variant check: observe.py:56-86)
+//   var_check_kernels.hpp  check_variants_samples_kernel (the variant check of a cohort's samples: assemble.py:157-208)
 //   assemble_kernels.hpp  consensus_kernel, new_variants_kernel, first_observed_kernel, extend_walk_kernel, extend_move_kernel
 //                       (consensus sequences and assembly extension over labelled pileups: assemble.py:431-585)
 // This file: the host side of the C ABI (shape checks, grid sizing, dispatch, the loop drivers).  Every refusal goes
@@ -76,6 +77,7 @@
 #include "exchange.hpp"
 #include "aln_walk.hpp"
 #include "observe_kernels.hpp"
+#include "var_check_kernels.hpp"
 #include "assemble_kernels.hpp"
 
 
@@ -2693,6 +2695,64 @@ extern "C" int mxm_observe_bases_labelled(const mxm_aln_columns *cols, const uin
                                           void *stream) {
     return observe_bases_impl<true>("mxm_observe_bases_labelled", cols, is_reverse, label, n_labels, min_mq, min_bq, L,
                                     counts, stream);
+}
+
+// ------------------------------------------------------------------------------------------
+// The variant check of a cohort's samples over their pileups (var_check_kernels.hpp).  Every refusal comes before the
+// first HIP call.  The host tables go into stream-ordered memory of the call's own (from pageable memory: the runtime has
+// taken the bytes when hipMemcpyAsync returns), released behind the kernel; nothing is waited for.
+// ------------------------------------------------------------------------------------------
+static_assert(VCHK_MAX_L == MXM_VAR_CHECK_MAX_L, "the header states the kernel's cap");
+extern "C" int mxm_check_variants_samples(const uint32_t *counts, int32_t S, int64_t L, const int32_t *key_ptr, const int32_t *key,
+                                          int32_t H, const int32_t *site, const int32_t *site_key, int32_t n_sites,
+                                          int64_t max_pos, const int32_t *cand_host, const int32_t *ncand_host, int32_t ld,
+                                          double min_var_reads, double frac_var_reads, double var_fraction,
+                                          int32_t has_var_count, int32_t var_count, uint8_t *keep, int32_t *n_uniq,
+                                          int32_t *n_found, void *stream) {
+    const char *who = "mxm_check_variants_samples";
+    if (S < 0) return fail(-1, "%s: S < 0 (%d)", who, S);
+    if (ld != 4 && ld != 8 && ld != 16 && ld != 32 && ld != VCHK_MAX_LD)
+        return fail(-1, "%s: ld = %d: the candidate tables' row stride must be 4, 8, 16, 32 or 64", who, ld);
+    if (S == 0) return 0;
+    if (cand_host == nullptr || ncand_host == nullptr) return fail(-1, "%s: bad arguments (cand_host and ncand_host are required)", who);
+    int64_t n_cand = 0;
+    for (int32_t s = 0; s < S; ++s) {
+        const int32_t k = ncand_host[s];
+        if (k < 0 || k > ld) return fail(-1, "%s: sample %d has ncand = %d outside [0, %d]", who, s, k, ld);
+        for (int32_t i = 0; i < k; ++i) {
+            const int32_t h = cand_host[(int64_t)s * ld + i];
+            if (h < 0 || h >= H) return fail(-1, "%s: sample %d, candidate %d: haplogroup index %d outside [0, %d)", who, s, i, h, H);
+        }
+        n_cand += k;
+    }
+    if (counts == nullptr || key_ptr == nullptr || key == nullptr || keep == nullptr || (n_sites > 0 && (site == nullptr || site_key == nullptr)))
+        return fail(-1, "%s: bad arguments (counts, key_ptr, key and keep are required, site and site_key with n_sites > 0)", who);
+    if ((reinterpret_cast<uintptr_t>(counts) & 15) != 0) return fail(-1, "%s: counts must be 16-byte aligned", who);
+    if (L <= 0 || n_sites < 0) return fail(-1, "%s: bad shape (L = %lld, n_sites = %d)", who, (long long)L, n_sites);
+    if (max_pos >= L)
+        return fail(-1, "%s: max_pos = %lld: the tree's variants reach past the pileup (L = %lld)", who, (long long)max_pos, (long long)L);
+    if (L > VCHK_MAX_L)
+        return fail(-1, "%s: L = %lld: a sample's bitsets do not fit the kernel's LDS (L <= %d)", who, (long long)L, VCHK_MAX_L);
+    if (n_cand == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = vchk_lds_bytes(L);
+    RC_TRY(dynamic_lds_ok(reinterpret_cast<const void *>(&check_variants_samples_kernel), lds, "check_variants_samples_kernel"));
+    int32_t *tables = nullptr;
+    const size_t n_tab = (size_t)S * ld;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void **>(&tables), (n_tab + (size_t)S) * sizeof(int32_t), st));
+    hipError_t e = hipMemcpyAsync(tables, cand_host, n_tab * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) e = hipMemcpyAsync(tables + n_tab, ncand_host, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(check_variants_samples_kernel, dim3((unsigned)S), dim3(VCHK_THREADS), lds, st, counts, L, key_ptr, key,
+                           site, site_key, (int)n_sites, (const int32_t *)tables, (const int32_t *)(tables + n_tab), (int)ld,
+                           min_var_reads, frac_var_reads, var_fraction, (int)(has_var_count != 0), (int)var_count, keep, n_uniq,
+                           n_found);
+        e = hipGetLastError();
+    }
+    const hipError_t ef = hipFreeAsync(tables, st);
+    HIP_TRY(e);
+    HIP_TRY(ef);
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------------

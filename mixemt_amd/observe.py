@@ -6,6 +6,8 @@ The pileup of mixemt's variant check -- observe.ObservedBases (the reference's m
     obs.obs_at(pos, base=None, stranded=False), obs.total_obs(pos)            the reference's queries (observe.py:88-145)
     obs.obs_tab[pos]            a Counter of the position's observations, as the reference's attribute holds them
     count_bases_labelled(dcols, label, counts)     one table per label in one call (stats.write_statistics' tables)
+    observe_bases_many(cols_list, ...)             the pileups of a cohort's samples in one upload and one labelled call:
+                                                   a CohortPileup whose tables stay on the device (assign.finish_many)
 
 The reference walks pysam's get_aligned_pairs(matches_only=False) one tuple at a time (observe.py:56-86); here one
 library call (mxm_observe_bases, csrc/observe_kernels.hpp) counts every alignment's bases and gaps into the table.
@@ -134,6 +136,71 @@ def observe_bases(cols, min_mq=30, min_bq=30, ref_len=None):
     obs = ObservedBases(counts.cpu().numpy().view(numpy.uint32), min_mq, min_bq)
     obs.upload_s = dcols.upload_s
     return obs
+
+
+COHORT_PILEUP_BYTES = 1 << 30        # observe_bases_many's default budget for the [S][L][16] table
+
+
+class CohortPileup(object):
+    """
+    The pileups of a cohort's samples in ONE device tensor (observe_bases_many):
+        counts            int32 device tensor [S][L][16] in the bins of BINS; nothing is downloaded unless asked
+        n_samples, L, min_map_qual, min_base_qual
+        lengths           the samples' own pileup_length: rows of counts[s] past lengths[s] are zero
+        host(s)           an ObservedBases over a host copy of table s (downloaded on first use, cached): every query
+                          answers as observe_bases(cols_list[s]) does -- a position past the sample's own length has no
+                          observations in either
+    """
+
+    def __init__(self, counts, lengths, min_mq=30, min_bq=30):
+        self.counts = counts
+        self.n_samples, self.L = int(counts.shape[0]), int(counts.shape[1])
+        self.lengths = [int(n) for n in lengths]
+        self.min_map_qual, self.min_base_qual = min_mq, min_bq
+        self.upload_s = 0.0
+        self._host = {}
+
+    def __len__(self):
+        return self.n_samples
+
+    def host(self, s):
+        s = int(s)
+        if not 0 <= s < self.n_samples:
+            raise IndexError("sample index out of range")
+        got = self._host.get(s)
+        if got is None:
+            table = self.counts[s, :self.lengths[s]].cpu().numpy().view(numpy.uint32)
+            got = self._host[s] = ObservedBases(table, self.min_map_qual, self.min_base_qual)
+        return got
+
+
+def observe_bases_many(cols_list, min_mq=30, min_bq=30, ref_len=None, max_bytes=COHORT_PILEUP_BYTES):
+    """
+    observe_bases for the samples of a cohort in one upload and ONE labelled pileup call (the label of an alignment is
+    its sample): -> CohortPileup with counts [S][L][16], L = the largest pileup_length among the samples.  The table takes
+    S * L * 64 bytes (272 MB for 256 samples at L = 16 589); above max_bytes (default 1 GiB) this raises ValueError and
+    the caller splits the cohort -- nothing is chunked silently.
+    """
+    from .alignments import concat_columns
+    cols_list = list(cols_list)
+    if not cols_list:
+        raise ValueError("observe_bases_many: no samples")
+    lengths = [pileup_length(cols, min_mq, ref_len) for cols in cols_list]
+    n, L = len(cols_list), max(lengths)
+    need = n * L * 64
+    if need > int(max_bytes):
+        raise ValueError("observe_bases_many: %d samples x %d positions need %d bytes of pileup tables, above the budget of "
+                         "%d bytes (max_bytes): split the cohort" % (n, L, need, int(max_bytes)))
+    dev = require_gpu()
+    joined, aln0 = concat_columns(cols_list)
+    dcols = DeviceColumns(joined, dev)
+    label = torch.from_numpy(numpy.repeat(numpy.arange(n, dtype=numpy.int32), numpy.diff(aln0))).to(dev)
+    counts = torch.zeros((n, L, 16), dtype=torch.int32, device=dev)
+    if len(joined) and L:
+        count_bases_labelled(dcols, label, counts, min_mq, min_bq)
+    pileup = CohortPileup(counts, lengths, min_mq, min_bq)
+    pileup.upload_s = dcols.upload_s
+    return pileup
 
 
 class ObservedBases(object):
