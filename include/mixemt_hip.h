@@ -164,6 +164,7 @@ int mxm_build_em_matrix_lut_rows(const uint8_t *Ecode, int64_t lde, const double
  * 704) distinct values, or -- long rows -- more than 5120 marker entries are NOT written: their indices are
  * appended to fallback[] (device int64[R], *n_fallback = how many, device) and the caller builds them with
  * mxm_build_em_matrix_lut (order = fallback, R = *n_fallback; any order of the list; every row at most once).
+ * The entries of fallback[] past *n_fallback are left alone, and so are the pad columns [H, ldm) of M (in all four builds).
  */
 int mxm_build_em_matrix_sparse(const uint8_t *maj, const double *lhit, const double *lmiss,
                                const int32_t *mk_ptr, const uint16_t *mk_hap, const uint8_t *mk_base,
@@ -177,6 +178,10 @@ int mxm_build_em_matrix_sparse(const uint8_t *maj, const double *lhit, const dou
  * (mxm_encode_rows) is needed, and with M == NULL no dense matrix is written at all:
  *     record = codes[ldc] ++ P table[ndist] ++ table of the log sums themselves [ndist]
  * (P = exp(sum - rowmax[r]); code 0 = the value of a haplogroup without a deviating marker in the window).
+ * rowmax[r] is the record's shift, the largest entry of its table of log sums: that is max_h M[r][h] whenever some
+ * haplogroup holds code 0's value or that value is not the largest -- every row of a real tree -- and LARGER than every
+ * cell of the row when all H haplogroups carry a deviating marker in the row's window and the marker-free value, which
+ * the table lists all the same, is the largest (P is then below 1 throughout; every consumer uses rowmax as the shift only).
  * Rows of 257 .. 705 distinct values get a record with 16-bit codes ("wide", round 6; 2 * ldc bytes of codes).
  * Rows that get no record have ndist[r] = 0: the rows on the fallback list (as above), which the caller builds
  * densely; with M given their dense row is NOT written either (the list says which).  stats[0] = bytes used,
@@ -217,6 +222,8 @@ int mxm_linearize(const double *M, int64_t ldm, int64_t R, int32_t H,
  * get there: every cell is finite and >= k * log(0.0033), so the best-supported haplogroup of a row
  * keeps P = 1 and would need ln p < -745 while the row's weight pulls it up every iteration.
  * props[B][H] = exp(ln_props[B][H]) (theta_k), w[R] fp64 weights (NULL = all 1).
+ * P is what mxm_linearize wrote, its pad columns [H, ldp) included: they are 0 (an odd H reads the column beside its
+ * last one); the pad columns of M are never read.  `state` is only read; `ws` needs no more than a double's alignment.
  * With several ranks the caller all-reduces (SUM) colsum before mxm_m_finalize.
  */
 int mxm_em_iter(const double *M, int64_t ldm, const double *P, int64_t ldp,
@@ -234,6 +241,8 @@ int mxm_em_iter(const double *M, int64_t ldm, const double *P, int64_t ldp,
  *   else ln_cur := ln_new, props_cur := exp(ln_new)
  * After the loop stops: ln_cur = log theta_k, ln_new = log theta_{k+1} -- the pair the
  * reference returns (posterior one step behind the proportions).  props_cur = exp(ln_cur).
+ * A restart with state[b].done != 0 is left alone: its rows of ln_cur / ln_new / props_cur and its state are not written.
+ * colsum is only read.
  */
 int mxm_m_finalize(const double *colsum, double *ln_cur, double *ln_new,
                    double *props_cur, int32_t H, int32_t B, double tol,
@@ -272,8 +281,11 @@ int mxm_em_loop_f32(const float *P, int64_t ldp, const double *w, int64_t R, int
  *                           (and is the size that would have sufficed) -- the caller repeats the call with that much
  *   mxm_encode_rows         M -> records (byte-coded pass over all rows, then a 16-bit pass over what it left);
  *                           stats[0] = bytes asked for, stats[1] = rows left dense (device int64[2]);
- *                           needs an even H in [66, 8192], even ldm, 16-byte aligned M and rec
- *   mxm_decode_rows         P[r][:] = row r decoded, coded rows only (tests; posterior passes)
+ *                           needs H in [65, 8192], ldm >= H (odd or even), M at a double's alignment, a 16-byte aligned
+ *                           rec of at least one full byte-coded record (ldc + 4096 bytes); the pad columns of M are
+ *                           never read, and nothing is written at or past rec + rec_bytes
+ *   mxm_decode_rows         P[r][:] = row r decoded, coded rows only (tests; posterior passes): the rows without a
+ *                           record and the pad columns [H, ldp) of P are left alone
  *   mxm_em_iter_coded / mxm_em_loop_coded   = mxm_em_iter / mxm_em_loop over a coded matrix
  *                           (w[R] indexes all rows, coded or not; one restart per pass -- beside a quad dictionary
  *                           full tiles of mxm_restart_tile_coded() = 3 restarts share a pass, em.py:117-161 runs them
@@ -285,7 +297,8 @@ typedef struct mxm_coded {
     const int32_t *ndist;        /* [R] table entries of row r: 1..256 byte codes, 257..1024 16-bit codes ("wide"),
                                     0 = row r is one of the dense rest */
     int64_t        R;            /* rows, coded or not */
-    const double  *P_rest;       /* [R_rest][ldp_rest] linearised rows that did not code (NULL if none) */
+    const double  *P_rest;       /* [R_rest][ldp_rest] linearised rows that did not code (NULL if none): 16-byte aligned,
+                                    ldp_rest even and >= H, pad columns 0 (what mxm_linearize writes) */
     int64_t        ldp_rest;
     const double  *w_rest;       /* their weights (NULL = 1) */
     int64_t        R_rest;
@@ -403,7 +416,7 @@ int mxm_em_loop_coded(const mxm_coded *c, const double *w, int32_t H, int32_t B,
  *                      row0_host, more than 2^31 - 1 tiles, or cap too small); tiles_host[cap] (nullable: count only)
  *                      receives the tiles in sample order, tile0_host[S + 1] (nullable) each sample's first tile.
  *   mxm_samples_workspace_bytes   scratch for a plan of n_tiles tiles: the tile table, one partial row of H doubles
- *                      per tile, a fault word per tile.
+ *                      per tile, a fault word per tile.  `ws` must be 16-byte aligned (-1 otherwise).
  *   mxm_em_iter_samples   one E+M pass for every unfinished sample: colsum[s][h] = T_sh as mxm_em_iter defines it, from
  *                      sample s's rows under props[s] (em.py:80-88).  Samples with state[s].done != 0 are skipped and
  *                      their colsum rows left untouched.  colsum[s] is the same bits on every run, whichever other samples
@@ -465,7 +478,9 @@ int mxm_em_loop(const double *M, int64_t ldm, const double *P, int64_t ldp,
  * E-step with the reference's semantics, writing the posterior -- em.py:80-83:
  *   out[r][h] = (ln_props[h] + M[r][h]) - logsumexp_h(ln_props + M[r])
  * mode 0: store; mode 1: out = logaddexp(out, value) (multi-run fold, em.py:156).
- * colsum (nullable): also the M-step sums sum_r w[r]*exp(out) (em.py:87-88).
+ * colsum (nullable): also the M-step sums sum_r w[r]*exp(out) (em.py:87-88); ws / ws_bytes as for mxm_em_iter
+ * (mxm_workspace_bytes(R, H, 1)), only needed with colsum.  The pad columns [H, ldo) of out are left alone, those of M
+ * never read.
  */
 int mxm_em_step(const double *M, int64_t ldm, const double *w,
                 const double *ln_props, int64_t R, int32_t H,
