@@ -1,0 +1,112 @@
+"""
+Inputs of the accuracy tests (tests/test_exact_ref.py on the CPU, tests/test_gpu_accuracy.py on the device): small, but
+where kernels go wrong.  Everything comes from oracle/, mixemt_amd.synth and numpy.
+
+  * matrices up to H = 5408: REAL rows -- c_oracle.build_em_matrix over a sub-tree of Build 17 (haps[300:300 + H]; all of
+    Build 17 at 5408) on synth_reads (700 rows of 150 bp, three more of 4000 bp: rows beyond 1024 distinct values at
+    full width -- the dense rest of a records plan; 400-bp rows hold about a hundred -- all drawn from contributor 0, the
+    haplogroup that holds 0.6 in the skewed vector: a converged state explains its rows) and synth_pairs (257 merged
+    fragments: rows of several hundred distinct values, wide records), contributors (0, H // 2, H - 1);
+  * wider than Build 17 (8192, 8200) and H <= 64: the few-values-per-row matrices of
+    test_gpu_coded.py::test_shapes_and_ragged_ends;
+  * weights: integers 1 .. 4 plus one zero weight;
+  * two proportion vectors per matrix: "dirichlet" = rng.dirichlet([1] * H), and "skewed", the converged regime:
+    ln p ~ U(-250, -5), then ln p[[0, H // 2]] = log([0.6, 0.3]) and ln p[H - 1] = log(1e-12).  Nothing is normalised:
+    the kernels take any positive vector, and so does the reference.
+"""
+import numpy
+
+from oracle import c_oracle
+
+N_READS, N_LONG, N_PAIRS, LONG_READ = 700, 3, 257, 4000
+_tables = {}
+_matrices = {}
+
+
+def tables_for(b17, n_haps):
+    from mixemt_amd import preprocess
+    refseq, phy, haps, tables = b17
+    if n_haps == len(haps):
+        return tables
+    if n_haps not in _tables:
+        _tables[n_haps] = preprocess.HapVarTables.build(refseq, phy, haps[300:300 + n_haps])
+    return _tables[n_haps]
+
+
+def real_rows(b17, n_haps, kind):
+    """kind "reads": 700 rows of 150-bp reads + 3 of 4000-bp reads (the LAST three rows); "pairs": 257 merged fragments.
+    The fp64 log matrix with the reference's bits (C oracle), built once per (width, kind) and never written to."""
+    from mixemt_amd import synth
+    key = (n_haps, kind)
+    if key not in _matrices:
+        refseq = b17[0]
+        tables = tables_for(b17, n_haps)
+        contrib = (0, n_haps // 2, n_haps - 1)
+        if kind == "reads":
+            parts = [synth.synth_reads(tables, len(refseq), N_READS, seed=n_haps, contrib=contrib),
+                     synth.synth_reads(tables, len(refseq), N_LONG, seed=n_haps + 1, contrib=contrib, read_len=LONG_READ,
+                                       props=(1.0, 0.0, 0.0))]
+        else:
+            parts = [synth.synth_pairs(tables, len(refseq), N_PAIRS, seed=n_haps, contrib=contrib)]
+        mats = [c_oracle.build_em_matrix(tables.expected, tables.lhit, tables.lmiss, row_ptr, site, obs, n_haps)
+                for row_ptr, site, obs, _ in parts]
+        mat = numpy.ascontiguousarray(numpy.concatenate(mats))
+        mat.setflags(write=False)
+        _matrices[key] = mat
+    return _matrices[key]
+
+
+def few_values(n_rows, n_haps):
+    """test_gpu_coded.py::test_shapes_and_ragged_ends' matrices: at most 40 distinct values per row."""
+    key = (n_haps, "few%d" % n_rows)
+    if key not in _matrices:
+        rng = numpy.random.default_rng(n_rows + n_haps)
+        few = rng.normal(-20.0, 6.0, size=(n_rows, 40))
+        mat = numpy.take_along_axis(few, rng.integers(0, 40, size=(n_rows, n_haps)), axis=1)
+        mat.setflags(write=False)
+        _matrices[key] = mat
+    return _matrices[key]
+
+
+def weights(n_rows, seed=0):
+    rng = numpy.random.default_rng(1000 + seed + n_rows)
+    wts = rng.integers(1, 5, size=n_rows).astype(numpy.float64)
+    if n_rows > 1:
+        wts[n_rows // 3] = 0.0
+    return wts
+
+
+def prop_vectors(n_haps, seed=0):
+    """{"dirichlet": (props, ln_props), "skewed": (props, ln_props)}: props = exp(ln_props) for the skewed vector and
+    ln_props = log(props) for the Dirichlet one, both in fp64 -- the two arrays a kernel may read."""
+    rng = numpy.random.default_rng(77 + seed + n_haps)
+    p = rng.dirichlet([1.0] * n_haps)
+    ln = rng.uniform(-250.0, -5.0, size=n_haps)
+    ln[[0, n_haps // 2]] = numpy.log([0.6, 0.3])
+    ln[n_haps - 1] = numpy.log(1e-12)
+    return {"dirichlet": (p, numpy.log(p)), "skewed": (numpy.exp(ln), ln)}
+
+
+def linearise(mat):
+    """exp(M - rowmax) in fp64 on the host: what the CPU test feeds the reference (the device tests read the device's P)."""
+    mat = numpy.asarray(mat)
+    return numpy.exp(mat - mat.max(axis=1, keepdims=True))
+
+
+# (name, width, how to get the log matrix): every matrix the two test modules use
+LINEAR_WIDTHS_REAL = (65, 66, 1023, 1024, 1025, 2050, 5408)
+LOG_WIDTHS = (1, 2, 17, 64, 8200)
+
+
+def all_inputs(b17):
+    """Every (label, M, w) of section 5, for the CPU test."""
+    for n_haps in LINEAR_WIDTHS_REAL:
+        reads = real_rows(b17, n_haps, "reads")
+        yield "reads %d" % n_haps, reads, weights(len(reads))
+        if n_haps in (66, 5408):
+            pairs = real_rows(b17, n_haps, "pairs")
+            yield "pairs %d" % n_haps, pairs, weights(len(pairs))
+    yield "reads[:37] 5408", real_rows(b17, 5408, "reads")[:37], weights(37)
+    for n_haps in (8192,) + LOG_WIDTHS:
+        mat = few_values(700, n_haps)
+        yield "few values %d" % n_haps, mat, weights(700)
