@@ -161,7 +161,8 @@ int mxm_build_em_matrix_lut_rows(const uint8_t *Ecode, int64_t lde, const double
  * fragment, preprocess.py:118-138, and two thirds of 2 x 150 paired-end fragments observe more than 64 sites);
  * the row's distinct masks are deduplicated and each one's sum is formed in signature order from 0.0, as
  * prob_for_vars does (preprocess.py:86-96).  Rows with more than 128 observations, more than 352 (long rows:
- * 704) distinct values, or -- long rows -- more than 5120 marker entries are NOT written: their indices are
+ * 704) distinct non-zero MASKS (two masks whose sums coincide count as two: the limit is the hash table's, not the
+ * row's number of distinct values), or -- long rows -- more than 5120 marker entries are NOT written: their indices are
  * appended to fallback[] (device int64[R], *n_fallback = how many, device) and the caller builds them with
  * mxm_build_em_matrix_lut (order = fallback, R = *n_fallback; any order of the list; every row at most once).
  * The entries of fallback[] past *n_fallback are left alone, and so are the pad columns [H, ldm) of M (in all four builds).
@@ -329,7 +330,8 @@ typedef struct mxm_coded {
 size_t mxm_coded_bytes(int64_t R, int32_t H);
 /*
  * mxm_build_quads    records -> quad records (device work on `stream`, no allocation): qoff[R] / nquad[R] for EVERY row
- *                    (0 for rows without a byte-coded record and for rows with more than 256 distinct quads); the
+ *                    (0 for rows without a byte-coded record and for rows with more than 256 distinct quads -- counted
+ *                    over the record's ldc / 4 code dwords, pad codes 0: where ldc - H >= 4 the all-pad quad is one of them); the
  *                    records go to qrec[0 .. qrec_bytes) by a bump allocator (64 KB reserved at a time by each of at most
  *                    5120 waves: up to 5120 x 64 KB are open, i.e. reserved and partly unused, when the call ends),
  *                    stats[0] = bytes reserved (a record that no longer fits is not written and its row keeps

@@ -182,7 +182,9 @@ int mxm_samples_tile_rows(void);
 int mxm_set_min_rows_per_wg(int32_t n);
 
 /* Test knob: distinct non-zero masks a row of the marker build kernel may have before it goes to the
- * fallback list (negative = the kernel's own limit, the default); lowering it drives ordinary rows through the fallback path. */
+ * fallback list (negative = the kernel's own limit, the default); lowering it drives ordinary rows through the fallback path.
+ * One number for both instances, each capped at its own limit: min(n, 352) for rows of up to 64 observations, min(n, 704)
+ * for the rows of 65 .. 128. */
 int mxm_set_sparse_max_distinct(int32_t n);
 
 #ifdef __cplusplus

@@ -19,7 +19,8 @@
 //     each one's sum is formed exactly as the reference forms it -- start at 0.0, add the n terms in order --
 //     so every cell carries the bits the cell-by-cell kernels produce;
 //   * the row is written from that table: 43 KB of stores per row instead of 2e11 additions per 10^6 rows.
-// Rows with more than 128 observations, or more than 352 distinct non-zero masks, are appended to
+// Rows with more than 128 observations, or more than 352 distinct non-zero masks (704 in the long rows' instance, which
+// also hands over a row of more than 5120 marker entries), are appended to
 // `fallback` for the cell-by-cell kernel (3 % of synth-v1 rows).  Between rows both LDS arrays are zero: a mask
 // is cleared by the thread that reads it, a table slot through the compacted list of occupied slots.
 // Round 6: rows of 65 .. 128 observations (merged 2 x 150 mates: two thirds of paired-end fragments; 250-bp reads) have

@@ -645,7 +645,8 @@ def build_em_records_device(tables, row_ptr, site, obs, dense=False, cap=None, r
     (one byte per haplogroup + the row's distinct values) -- what em.EmPlan(storage="coded") otherwise
     makes from the dense matrix with a pass of its own.  dense=False: NO dense matrix is written (5.5 GB
     instead of 43 GB at 10^6 x 5408; 10^7 rows fit one GPU); rows the marker kernel cannot take (more than
-    128 observations, more than 5120 marker entries, more than 704 distinct values: 2 % of 150-bp reads, 4 % of merged mates) are built densely by the lookup-table kernel and
+    128 observations; from 65 observations more than 5120 marker entries; more than 352 distinct masks, 704 from 65
+    observations: 2 % of 150-bp reads, 4 % of merged mates) are built densely by the lookup-table kernel and
     coded from there (mxm_encode_rows: byte codes up to 256 values, 16-bit codes up to 1024) a slab (REST_SLAB_BYTES) at a
     time, so the detour never holds more than one slab of dense rows (round 4 built all of them at once: 1.4 GB at
     10^6 rows, 14 GB at 10^7); what remains (more than 1024 values: none on build_em_matrix's rows) stays dense in `m_rest`.
