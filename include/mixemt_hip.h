@@ -15,11 +15,24 @@
  * Conventions
  *   - every pointer is a DEVICE pointer unless its name ends in _host;
  *   - `stream` is a hipStream_t passed as void* (NULL = default stream);
- *     every call only enqueues work on it unless stated otherwise;
+ *     every call only enqueues work on it unless stated otherwise: every
+ *     kernel, memset and copy of a call is ordered on `stream` behind what the
+ *     caller enqueued there before, whether or not that has finished.  An
+ *     entry that waits for the stream says so in its own paragraph;
+ *   - a `*_host` array (and the HOST `rows` of mxm_new_variants /
+ *     mxm_extend_assign) is read before the call returns -- from pageable or
+ *     pinned memory alike -- and may be changed or freed once it has returned;
  *   - matrices are row-major with an explicit leading dimension (in elements);
  *   - return value: 0 = ok, negative = error (text via mxm_last_error());
  *   - no allocation inside: the caller owns every buffer including `ws`
- *     (size from mxm_workspace_bytes), so calls are hipGraph-capturable;
+ *     (size from mxm_workspace_bytes), so the calls that only enqueue are
+ *     hipGraph-capturable.  Not meant to be captured: the entries that take
+ *     stream-ordered memory of their own (hipMallocAsync / hipFreeAsync on
+ *     `stream`: the four alignment-walk entries and the cohort's variant
+ *     check), the entries that upload a host table on every call (the
+ *     `_samples` entries: a replay would not upload it again) and the loops.
+ *     tests/test_gpu_stream_contract.py holds every entry to its class, on a
+ *     stream that is still busy when the call is made;
  *   - work goes to the calling thread's current device; one process (or thread) per GPU.
  *     mxm_last_error() is per thread.  Tuning / measurement knobs are NOT part of this
  *     boundary: they live in mixemt_hip_tuning.h.
@@ -253,7 +266,8 @@ int mxm_m_finalize(const double *colsum, double *ln_cur, double *ln_new,
  * fp32-STORAGE variant of the loop (opt-in; NOT the reference's arithmetic type for the stored
  * matrix): P is kept as float -- half the HBM bytes per iteration -- while every product, row sum
  * and column sum stays fp64.  One restart per pass.  ldp (floats) a multiple of 4, pad columns 0.
- * Everything else (w, props, colsum, state, finalize, posterior from the fp64 M) is unchanged.
+ * Everything else (w, props, colsum, state, finalize, posterior from the fp64 M) is unchanged;
+ * mxm_em_loop_f32 blocks the calling thread as mxm_em_loop does.
  */
 int mxm_linearize_f32(const double *M, int64_t ldm, int64_t R, int32_t H,
                       float *P, int64_t ldp, double *rowmax, void *stream);
@@ -290,7 +304,8 @@ int mxm_em_loop_f32(const float *P, int64_t ldp, const double *w, int64_t R, int
  *   mxm_em_iter_coded / mxm_em_loop_coded   = mxm_em_iter / mxm_em_loop over a coded matrix
  *                           (w[R] indexes all rows, coded or not; one restart per pass -- beside a quad dictionary
  *                           full tiles of mxm_restart_tile_coded() = 3 restarts share a pass, em.py:117-161 runs them
- *                           one after another over the same matrix)
+ *                           one after another over the same matrix).  mxm_em_iter_coded only enqueues.
+ *                           mxm_em_loop_coded blocks the calling thread as mxm_em_loop does.
  */
 typedef struct mxm_coded {
     const uint8_t *rec;          /* records */
@@ -426,12 +441,17 @@ int mxm_em_loop_coded(const mxm_coded *c, const double *w, int32_t H, int32_t B,
  *                      atomics).  A row with -inf everywhere and a nonzero weight makes ITS sample's sums NaN (em.py:81-87),
  *                      no other's.  A row without a record (ndist outside 1 .. 1024) poisons its sample's sums with NaN
  *                      and raises state[s].error = 1; the row is never dereferenced.  The tile table (16 bytes per tile) is
- *                      made and uploaded by every call, ordered on `stream` (the call may wait for that copy; the kernels
- *                      are only enqueued); the caller follows it with mxm_m_finalize(B = S).
+ *                      made and uploaded by every call, ordered on `stream`, from pageable memory of the call's own: the
+ *                      runtime has taken the bytes when the copy call returns.  The kernels are only enqueued, and so is
+ *                      the copy at the table sizes measured (a few hundred bytes, on a stream with work pending:
+ *                      profiles/streams/README.md); HIP lets a runtime hold a larger pageable upload until the stream has
+ *                      got there, which changes the call's host time, never its results or their order.
+ *                      The caller follows it with mxm_m_finalize(B = S).
  *   mxm_em_loop_samples   mxm_em_loop_coded over S samples -- em.py:126-143 for each: {pass; column reduce;
  *                      mxm_m_finalize with B = S} in chunks of check_every iterations, one read-back of the states per
  *                      chunk, until every sample is done.  Plain launches on `stream`: no persistent grid, no graph.
- *                      tol / max_iter are one value for the batch.  Blocks; state_host[S] receives the final states.
+ *                      tol / max_iter are one value for the batch.  mxm_em_loop_samples blocks the calling thread; state_host[S]
+ *                      receives the final states.
  *                      -1 when a sample's error was raised.
  * mxm_em_iter_samples and mxm_em_loop_samples return -1 WITHOUT touching the device for: c->qrec != NULL, c->R_rest != 0, an odd H or one outside
  * [66, 8192], an empty sample, a row0_host that is not ascending, row0_host[S] != c->R.
@@ -668,7 +688,7 @@ int  mxm_observe_bases(const mxm_aln_columns *cols, const uint8_t *is_reverse, i
  * ZEROED by the caller, accumulated into); label[i] < 0: not counted.  Each table is the same bits as
  * mxm_observe_bases over that label's alignments alone, for any alignment order.  (stats.write_statistics, stats.py:138-171:
  * ObservedBases of each contributor's reads.)  Returns as mxm_observe_bases, and -1 for a label >= n_labels, naming the
- * first such alignment in index order.
+ * first such alignment in index order.  HOST, blocking, as mxm_observe_bases.
  */
 int  mxm_observe_bases_labelled(const mxm_aln_columns *cols, const uint8_t *is_reverse, const int32_t *label,
                                 int32_t n_labels, int32_t min_mq, int32_t min_bq, int64_t L, uint32_t *counts,

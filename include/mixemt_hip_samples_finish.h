@@ -22,6 +22,14 @@ extern "C" {
  * stands in it.  No float atomics.  Still MXM_VERSION 603: additions only.
  * ws: mxm_samples_finish_workspace_bytes(n_tiles of mxm_samples_plan, S, ld) bytes on the device, 16-byte aligned (the
  * tile table and the per-sample tables, uploaded by every call, ordered on `stream`; ld = 0 for mxm_votes_samples).
+ * STREAM: mxm_votes_samples, mxm_gather_columns_samples and mxm_assign_reads_samples only enqueue: the tables are copied
+ * from pageable host memory of the call's own (the caller's *_host arrays are copied there first, so they are read before
+ * the call returns whether they are pageable or pinned, and may be changed as soon as it has returned); the runtime has
+ * taken those bytes when the copy call returns.  At the table sizes measured (a few hundred bytes, on a stream with work
+ * pending: profiles/streams/README.md) the copies are only enqueued too; HIP lets a runtime hold a larger pageable upload
+ * until the stream has got there, which changes the call's host time, never its results or their order.  The loop entry
+ * is the exception: see its own paragraph.  None of the four is meant to be captured: a replay would not upload the
+ * tables again.
  *   mxm_votes_samples   assemble.py:115-123 per sample, over the concatenated records (one workgroup per tile of the
  *       plan, then one per sample): best[r] = first index of max_h (ln_props[s][h] + M[r][h]) for the rows of sample s (one
  *       run: the row normaliser drops out, see mxm_row_argmax_votes_coded); votes[s][h] = sum of w[r] (NULL: 1) over the
@@ -39,6 +47,8 @@ extern "C" {
  *       ln_new = log theta_{k+1}); a launch runs at most check_every iterations per unfinished sample and the host
  *       re-launches until every state is done.  e = exp(M - rowmax) is formed once per launch, in LDS for a sample of up
  *       to 9216 cells (R_s x ncol), else in E [R][ld] (nullable when every sample fits).  Samples with ncol 0 are left alone.
+ *       mxm_em_loop_samples_narrow blocks the calling thread (one read-back of the states per launch); state_host[S]
+ *       receives the final states.
  *   mxm_assign_reads_samples   assemble.py:284-334 per row under its sample's columns: X_c = (ln_theta[s][c] + M[r][c]) -
  *       (rowmax_r + log sum_c props[s][c] exp(M[r][c] - rowmax_r)) as mxm_em_step documents it (or minus lse[r] when lse is
  *       given: the first EM's full-width normaliser, for the unrefined assignment), v_c = X_c - log_props[s][c] (the

@@ -35,8 +35,11 @@ extern "C" {
  * site_key of every site none of its keys -- found or not, claimed before or not -- falls on (phylo.get_ancestral,
  * phylotree.py:317-336); a dropped one claims nothing.  Integer counts and bit-ORs only: the same bits for any thread
  * order and wherever the sample stands in the batch; no float atomics.
- * The host tables are uploaded by the call into stream-ordered memory of its own; the kernel is ordered on `stream` and
- * nothing is waited for.
+ * The host tables are uploaded by the call into stream-ordered memory of its own (hipMallocAsync / hipFreeAsync on `stream`:
+ * not meant to be captured), through a pageable copy of the call's own: cand_host / ncand_host are read before the call
+ * returns, from pageable or pinned memory alike.  The kernel is ordered on `stream` and nothing is waited for at the table
+ * sizes measured (S = 3, ld = 8: 108 bytes, on a stream with work pending; profiles/streams/README.md); HIP lets a runtime
+ * hold a larger pageable upload until the stream has got there, which changes the call's host time, never its results.
  * Refused with -1 WITHOUT touching the device: S < 0; ld not one of 4, 8, 16, 32, 64; cand_host / ncand_host NULL; an
  * ncand_host[s] outside [0, ld]; a candidate index outside [0, H); counts, key_ptr, key or keep NULL (site / site_key
  * with n_sites > 0); counts not 16-byte aligned; L <= 0 or n_sites < 0; max_pos >= L; L > MXM_VAR_CHECK_MAX_L.

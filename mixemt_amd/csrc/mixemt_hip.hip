@@ -2199,18 +2199,32 @@ static int finish_ws_check(const char *who, const void *ws, size_t ws_bytes, int
     return 0;
 }
 
-// the plan and the per-sample tables into the workspace, ordered on `stream` (from pageable memory: the runtime has
-// taken the bytes when the call returns)
+// the plan and the per-sample tables into the workspace, ordered on `stream`.  The caller's tables go through vectors of
+// the call's own, as the tiles do: from pageable memory the runtime has taken the bytes when hipMemcpyAsync returns
+// (without waiting for the stream: tests/test_gpu_stream_contract.py), from a caller's PINNED array it would read them
+// whenever the stream gets there, after the caller may have changed them.
 static int finish_upload(const int64_t *row0_host, int S, int64_t n_tiles, int ld, const int32_t *ncol_host, const int32_t *cols_host,
                          const int32_t *perm_host, const finish_ws &L, hipStream_t stream) {
     static thread_local std::vector<mxm_sample_tile> tiles;
+    static thread_local std::vector<int64_t> row0;
+    static thread_local std::vector<int32_t> ncol, cols, perm;
     tiles.resize((size_t)n_tiles);
     if (mxm_samples_plan(row0_host, S, tiles.data(), n_tiles, nullptr) != n_tiles) return -1;
     HIP_TRY(hipMemcpyAsync(L.tiles, tiles.data(), (size_t)n_tiles * sizeof(mxm_sample_tile), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemcpyAsync(L.row0, row0_host, ((size_t)S + 1) * sizeof(int64_t), hipMemcpyHostToDevice, stream));
-    if (ncol_host != nullptr) HIP_TRY(hipMemcpyAsync(L.ncol, ncol_host, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    if (cols_host != nullptr) HIP_TRY(hipMemcpyAsync(L.cols, cols_host, (size_t)S * ld * sizeof(int32_t), hipMemcpyHostToDevice, stream));
-    if (perm_host != nullptr) HIP_TRY(hipMemcpyAsync(L.perm, perm_host, (size_t)S * ld * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    row0.assign(row0_host, row0_host + (size_t)S + 1);
+    HIP_TRY(hipMemcpyAsync(L.row0, row0.data(), row0.size() * sizeof(int64_t), hipMemcpyHostToDevice, stream));
+    if (ncol_host != nullptr) {
+        ncol.assign(ncol_host, ncol_host + (size_t)S);
+        HIP_TRY(hipMemcpyAsync(L.ncol, ncol.data(), ncol.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    }
+    if (cols_host != nullptr) {
+        cols.assign(cols_host, cols_host + (size_t)S * ld);
+        HIP_TRY(hipMemcpyAsync(L.cols, cols.data(), cols.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    }
+    if (perm_host != nullptr) {
+        perm.assign(perm_host, perm_host + (size_t)S * ld);
+        HIP_TRY(hipMemcpyAsync(L.perm, perm.data(), perm.size() * sizeof(int32_t), hipMemcpyHostToDevice, stream));
+    }
     return 0;
 }
 
@@ -2700,7 +2714,8 @@ extern "C" int mxm_observe_bases_labelled(const mxm_aln_columns *cols, const uin
 // ------------------------------------------------------------------------------------------
 // The variant check of a cohort's samples over their pileups (var_check_kernels.hpp).  Every refusal comes before the
 // first HIP call.  The host tables go into stream-ordered memory of the call's own (from pageable memory: the runtime has
-// taken the bytes when hipMemcpyAsync returns), released behind the kernel; nothing is waited for.
+// taken the bytes when hipMemcpyAsync returns), released behind the kernel; nothing is waited for -- checked on a stream
+// with work pending (tests/test_gpu_stream_contract.py: the call returns at once, the tables are overwritten at return).
 // ------------------------------------------------------------------------------------------
 static_assert(VCHK_MAX_L == MXM_VAR_CHECK_MAX_L, "the header states the kernel's cap");
 extern "C" int mxm_check_variants_samples(const uint32_t *counts, int32_t S, int64_t L, const int32_t *key_ptr, const int32_t *key,
@@ -2739,9 +2754,13 @@ extern "C" int mxm_check_variants_samples(const uint32_t *counts, int32_t S, int
     RC_TRY(dynamic_lds_ok(reinterpret_cast<const void *>(&check_variants_samples_kernel), lds, "check_variants_samples_kernel"));
     int32_t *tables = nullptr;
     const size_t n_tab = (size_t)S * ld;
-    HIP_TRY(hipMallocAsync(reinterpret_cast<void **>(&tables), (n_tab + (size_t)S) * sizeof(int32_t), st));
-    hipError_t e = hipMemcpyAsync(tables, cand_host, n_tab * sizeof(int32_t), hipMemcpyHostToDevice, st);
-    if (e == hipSuccess) e = hipMemcpyAsync(tables + n_tab, ncand_host, (size_t)S * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    // both tables through one vector of the call's own (pageable): a caller's pinned array would be read when the stream
+    // gets there, after the caller may have changed it
+    static thread_local std::vector<int32_t> staged;
+    staged.assign(cand_host, cand_host + n_tab);
+    staged.insert(staged.end(), ncand_host, ncand_host + (size_t)S);
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void **>(&tables), staged.size() * sizeof(int32_t), st));
+    hipError_t e = hipMemcpyAsync(tables, staged.data(), staged.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
         hipLaunchKernelGGL(check_variants_samples_kernel, dim3((unsigned)S), dim3(VCHK_THREADS), lds, st, counts, L, key_ptr, key,
                            site, site_key, (int)n_sites, (const int32_t *)tables, (const int32_t *)(tables + n_tab), (int)ld,
