@@ -785,4 +785,6 @@ void mxm_exchange_destroy(mxm_exchange *x);
 #include "mixemt_hip_samples_finish.h"
 /* mixemt's variant check for the samples of a cohort, over pileups that stay on the device */
 #include "mixemt_hip_var_check.h"
+/* the assembly extension for the samples of a cohort: new variants and the walk + move over global labels */
+#include "mixemt_hip_assemble_samples.h"
 #endif /* MIXEMT_HIP_H */

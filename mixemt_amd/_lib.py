@@ -206,6 +206,14 @@ VARCHECK_SIGNATURES = {
                                                   c_ptr, c_i32, c_f64, c_f64, c_f64, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
+# a round of the assembly extension for the samples of a cohort over global labels (include/mixemt_hip_assemble_samples.h:
+# additions behind ABI version 603); their refusals are pinned in tests/test_assemble_samples_host.py
+ASSEMBLE_SAMPLES_SIGNATURES = {
+    "mxm_new_variants_samples": (ctypes.c_int, [c_ptr, c_i64, c_i32, c_ptr, c_ptr, c_i32, c_i64, c_ptr, c_ptr, c_ptr]),
+    "mxm_extend_assign_samples": (ctypes.c_int, [ctypes.POINTER(AlnColumns), c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i32,
+                                                 c_i32, c_i32, c_i32, c_i32, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
+}
+
 # the MXM_VERSION of include/mixemt_hip.h these signatures were written for; load() refuses any other
 ABI_VERSION = 603
 
@@ -243,7 +251,7 @@ def load():
         raise MixemtHipError("%s reports ABI version %s, this binding was written for %d: rebuild with "
                              "`python -m mixemt_amd.build --force`" % (LIB_PATH, have, ABI_VERSION))
     for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(FINISH_SIGNATURES.items())
-                                      + list(VARCHECK_SIGNATURES.items())):
+                                      + list(VARCHECK_SIGNATURES.items()) + list(ASSEMBLE_SAMPLES_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -327,3 +327,183 @@ def write_consensus_seqs(refseq, contribs, contrib_reads, args):
     seqs = call_consensus_all(refseq, contrib_reads, 1, args, strict=False, names=names)
     with open("%s.fa" % (args.cons_prefix), "w") as fa_out:
         fa_out.write(format_fasta((rec_id, desc, seqs[rec_id]) for rec_id, desc in records))
+
+
+# ---- the assembly stage of a cohort: -x and -b for ALL samples in shared rounds (assign.CohortContribReads) -----------------
+def _cohort_tables(cohort, args, ref_len, who):
+    """(L, zeroed counts[n_labels][L][16]) of a cohort, within its byte budget."""
+    from .assign import _cohort_budget
+    cache = cohort.__dict__.setdefault("_pileup_len", {})
+    key = (int(args.min_mq), int(ref_len))
+    if key not in cache:
+        cache[key] = observe.pileup_length(cohort.cols, args.min_mq, ref_len)
+    L = cache[key]
+    _cohort_budget(who, cohort.n_labels, L, cohort.max_bytes)
+    return L, torch.zeros((max(cohort.n_labels, 1), L, 16), dtype=torch.int32, device=cohort.labels.device)
+
+
+def _cohort_struct(cohort):
+    """The cohort's uploaded columns as mxm_aln_columns with the fragment column (mxm_extend_assign_samples reads it)."""
+    st = cohort.device_columns().struct()
+    frag = cohort.device_frag()
+    st.n_frag = cohort.n_frag
+    st.frag = frag.data_ptr() if frag.numel() else None
+    return st
+
+
+def _i32(values):
+    return (ctypes.c_int32 * max(len(values), 1))(*values)
+
+
+def extend_assemblies_many(refseq, cohort, args, samples=None):
+    """
+    extend_assemblies for the samples `samples` of an assign.CohortContribReads (default: those with more than one
+    contributor, bin/mixemt:329) in SHARED rounds: a round for all samples that are still moving is one labelled pileup
+    call that adds the pending alignments to counts[n_labels][L][16], one mxm_consensus, one mxm_new_variants_samples, one
+    mxm_extend_assign_samples, and one read-back of two counters per sample.  Per sample the labels, joined, keys and rounds
+    are those of extend_assemblies on the sample alone: its participants are its keys other than 'unassigned'; when one of
+    them has no alignments there are no new variants at all; at least one round is run; after its first round without a
+    move the sample is FROZEN (no 'unassigned' label and no participants are handed to the kernels), so nothing of it can
+    change while others run on; joined is the sample's own round number.  With args.verbose every sample's stderr text is
+    collected and written sample after sample, each block what its own extend_assemblies call writes.
+    The tables take n_labels x L x 64 bytes: ValueError above the cohort's max_bytes (assign.assign_reads_many).
+    Returns cohort, relabelled in place.
+    """
+    require_gpu()
+    lib = _lib.load()
+    n = cohort.n_samples
+    ref_len = len(refseq)
+    if samples is None:
+        samples = [s for s in range(n) if cohort.n_contribs(s) > 1]
+    samples = sorted(set(int(s) for s in samples))
+    if any(not 0 <= s < n for s in samples):
+        raise IndexError("extend_assemblies_many: sample index out of range")
+    if not samples:
+        return cohort
+    dev = cohort.labels.device
+    count = cohort.counts()
+    use_of, un_of, unassigned, text = {}, {}, {}, {}
+    for s in samples:
+        if "unassigned" not in cohort.keys[s]:
+            cohort.keys[s].append("unassigned")                      # (the reference's defaultdict gains the key here)
+        names = [name for name in cohort.keys[s] if name != "unassigned"]
+        if len(names) > 127:
+            raise ValueError("find_new_variants: %d contributors take part, at most 127" % len(names))
+        use = [cohort.label_of(s, name) for name in names]
+        live = bool(names) and ref_len > 0 and all(u is not None and count[u] > 0 for u in use)
+        use_of[s] = use if live else []
+        un_of[s] = cohort.label_of(s, "unassigned")
+        unassigned[s] = int(count[un_of[s]]) if un_of[s] is not None else 0
+        text[s] = ["\nAssembly extension step...\n"]
+    L, counts = _cohort_tables(cohort, args, ref_len, "extend_assemblies_many")
+    n_aln = len(cohort.cols)
+    lut = numpy.full(cohort.n_labels + 1, -1, dtype=numpy.int32)     # (the last entry serves label -1)
+    for s in samples:
+        for u in use_of[s]:
+            lut[u] = u
+    pending = torch.from_numpy(lut).to(dev)[cohort.labels.to(torch.int64)].contiguous() if n_aln else None
+    cons = torch.empty((max(cohort.n_labels, 1), max(ref_len, 1)), dtype=torch.uint8, device=dev)
+    newvar = torch.full((n, max(ref_len, 1)), -1, dtype=torch.int32, device=dev)
+    counters = torch.zeros((2, n), dtype=torch.int32, device=dev)   # [0]: new variants, [1]: moved alignments
+    frag_state = torch.empty(max(cohort.n_frag, 1), dtype=torch.int32, device=dev)
+    moved_owner = torch.empty(max(n_aln, 1), dtype=torch.int32, device=dev)
+    st = _cohort_struct(cohort)
+    dcols = cohort.device_columns()
+    active = list(samples)
+    run = 1
+    while active:
+        use_ptr, use, un = [0], [], [-1] * n
+        for s in range(n):
+            if s in active:
+                use.extend(use_of[s])
+                un[s] = -1 if un_of[s] is None else un_of[s]
+            use_ptr.append(len(use))
+        counters.zero_()
+        if use and n_aln:
+            if pending is not None:
+                observe.count_bases_labelled(dcols, pending, counts, args.min_mq, args.min_bq)
+            _lib.check(lib.mxm_consensus(counts.data_ptr(), cohort.n_labels, L, ref_len, int(args.cons_cov), 1, cons.data_ptr(),
+                                         None, None, current_stream()), "mxm_consensus")
+            _lib.check(lib.mxm_new_variants_samples(cons.data_ptr(), cons.stride(0), cohort.n_labels, _i32(use), _i32(use_ptr),
+                                                    n, ref_len, newvar.data_ptr(), counters[0].data_ptr(), current_stream()),
+                       "mxm_new_variants_samples")
+            if any(un[s] >= 0 and use_ptr[s + 1] > use_ptr[s] for s in range(n)):
+                _lib.check(lib.mxm_extend_assign_samples(ctypes.byref(st), cohort.aln_sample.data_ptr(), cohort.labels.data_ptr(),
+                                                         cohort.joined.data_ptr(), _i32(un), _i32(use), _i32(use_ptr), n,
+                                                         cohort.n_labels, run, int(args.min_mq), int(args.min_bq),
+                                                         newvar.data_ptr(), ref_len, frag_state.data_ptr(),
+                                                         moved_owner.data_ptr(), counters[1].data_ptr(), current_stream()),
+                           "mxm_extend_assign_samples")
+        got = counters.cpu().numpy()                                 # ONE read-back per round: two counters per sample
+        any_moved = False
+        for s in list(active):
+            n_new, moved = int(got[0, s]), int(got[1, s])
+            cohort.rounds[s] += 1
+            cohort.round_log[s].append((moved, unassigned[s], n_new))
+            text[s].append("  %d: %d/%d reads assigned using %d variants\n" % (run, moved, unassigned[s], n_new))
+            unassigned[s] -= moved
+            any_moved = any_moved or moved > 0
+            if not moved:
+                active.remove(s)                                     # frozen: its labels, joined and rounds stay
+        # (moved_owner holds global labels, -1 for what did not move: the labels of the next additive pileup as they are)
+        pending = moved_owner if any_moved else None
+        run += 1
+    if args.verbose:
+        for s in samples:
+            sys.stderr.write("".join(text[s]) + "\n")
+    return cohort
+
+
+def call_consensus_many(refseq, cohort, min_cov, args, strict=True):
+    """
+    call_consensus_all for every sample of an assign.CohortContribReads -> one {name: str} per sample over the sample's
+    keys: ONE labelled pileup over the global labels, ONE mxm_consensus, ONE mxm_first_observed when strict is False and
+    some position is tied (the global labels are its tables; its scratch takes the tables' size again), ONE download.  The
+    strings equal call_consensus_all of cohort.sample(s); a name without alignments gives "".
+    """
+    require_gpu()
+    ref_len = len(refseq)
+    out = [{name: "" for name in keys} for keys in cohort.keys]
+    count = cohort.counts()
+    if ref_len == 0 or not len(cohort.cols) or not count.any():
+        return out
+    lib = _lib.load()
+    L, counts = _cohort_tables(cohort, args, ref_len, "call_consensus_many")
+    observe.count_bases_labelled(cohort.device_columns(), cohort.labels, counts, args.min_mq, args.min_bq)
+    cons, tied, n_tied = _consensus_device(counts, ref_len, min_cov, strict, want_tied=not strict)
+    if n_tied:
+        st = cohort.device_columns().struct()
+        _lib.check(lib.mxm_first_observed(ctypes.byref(st), cohort.labels.data_ptr(), cohort.joined.data_ptr(), cohort.n_labels,
+                                          int(args.min_mq), int(args.min_bq), ref_len, tied.data_ptr(), cons.data_ptr(),
+                                          current_stream()), "mxm_first_observed")
+    host = cons.cpu().numpy()
+    for s, keys in enumerate(cohort.keys):
+        for name in keys:
+            lab = cohort.label_of(s, name)
+            if lab is not None and count[lab] > 0:
+                out[s][name] = host[lab].tobytes().decode("ascii")
+    return out
+
+
+def write_consensus_seqs_many(refseq, contribs_list, cohort, args, prefixes):
+    """
+    write_consensus_seqs for every sample of an assign.CohortContribReads: prefixes[s] + '.fa' holds what
+    write_consensus_seqs(refseq, contribs_list[s], cohort.sample(s), args) writes under that prefix -- the majority
+    consensus (min_cov 1, strict=False) of every contributor in order (looking one up makes it a key of the sample), then
+    of 'unassigned' when it is a key -- from ONE call_consensus_many.  args.cons_prefix is not read.
+    """
+    if len(contribs_list) != cohort.n_samples or len(prefixes) != cohort.n_samples:
+        raise ValueError("write_consensus_seqs_many: one contributor table and one prefix per sample are needed")
+    records = []
+    for s, contribs in enumerate(contribs_list):
+        for con, _, _ in contribs:
+            if con not in cohort.keys[s]:
+                cohort.keys[s].append(con)
+        recs = [(con, hap) for con, hap, _ in contribs]
+        if "unassigned" in cohort.keys[s]:
+            recs.append(("unassigned", ""))
+        records.append(recs)
+    seqs = call_consensus_many(refseq, cohort, 1, args, strict=False)
+    for s, recs in enumerate(records):
+        with open("%s.fa" % (prefixes[s]), "w") as fa_out:
+            fa_out.write(format_fasta((rec_id, desc, seqs[s][rec_id]) for rec_id, desc in recs))

@@ -957,3 +957,179 @@ def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refin
                   "row_label": label, "route": "batch", "var_check": var_route[s],
                   "posterior": post[lo:hi, :int(ncol[j])] if post is not None else None}
     return out
+
+
+# ---- the third stage of a cohort run: one label per alignment for ALL samples (assign_reads' counterpart) --------------------
+COHORT_TABLES_BYTES = 4 << 30       # default budget for the [n_labels][L][16] tables of the cohort's assembly stage: a cap,
+                                    # not a measurement
+
+
+def _cohort_budget(who, n_labels, L, max_bytes):
+    need = int(n_labels) * int(L) * 64
+    if need > int(max_bytes):
+        raise ValueError("%s: %d labels x %d positions need %d bytes of pileup tables, above the budget of %d bytes "
+                         "(max_bytes): split the cohort" % (who, n_labels, L, need, int(max_bytes)))
+
+
+def _cohort_label_plan(finished, n_rows):
+    """
+    The global labels of a cohort from finish_many's list (host only): with K_s = len(contribs), sample s owns the labels
+    lab0[s] .. lab0[s] + K_s -- its contributors in order, then its 'unassigned' (the slot is always reserved; no alignment
+    carries it when K_s == 1, as assign_reads has no such label then).  n_rows[s]: the sample's rows.
+    -> (lab0 int64 [S + 1], names per sample as assign_reads names its labels, keys per sample as it orders them, the rows'
+    GLOBAL labels per sample: numpy int32 [R_s]).  A sample without contributors has no names, no keys and every row -1.
+    """
+    lab0 = numpy.zeros(len(finished) + 1, dtype=numpy.int64)
+    names, keys, rows = [], [], []
+    for s, fin in enumerate(finished):
+        contribs = fin["contribs"]
+        k = len(contribs)
+        lab0[s + 1] = lab0[s] + k + 1
+        names.append([con[0] for con in contribs] + (["unassigned"] if k > 1 else []))
+        keys.append(list(fin["assigned"]) if k else [])
+        if k == 0:
+            row = numpy.full(int(n_rows[s]), -1, dtype=numpy.int64)
+        elif k == 1:
+            row = numpy.full(int(n_rows[s]), lab0[s], dtype=numpy.int64)
+        else:
+            local = numpy.asarray(fin["row_label"], dtype=numpy.int64)
+            if local.shape != (int(n_rows[s]),):
+                raise ValueError("assign_reads_many: sample %d has %d rows of fragments and %d row labels"
+                                 % (s, int(n_rows[s]), local.size))
+            if local.size and int(local.max()) >= k:
+                raise ValueError("assign_reads_many: sample %d has a row label >= its %d contributors" % (s, k))
+            row = numpy.where(local >= 0, lab0[s] + local, lab0[s] + k)
+        rows.append(row.astype(numpy.int32))
+    if int(lab0[-1]) >= 2 ** 31:
+        raise ValueError("assign_reads_many: more than 2^31 - 1 labels")
+    return lab0, names, keys, rows
+
+
+class CohortContribReads(object):
+    """
+    assign_reads' result for ALL samples of a cohort (assign_reads_many): ONE int32 label per alignment over the
+    concatenated columns, the labels GLOBAL -- sample s owns lab0[s] .. lab0[s] + K_s (its contributors, then 'unassigned');
+    -1 stays -1.
+        cols_list, cols, aln0    the samples' columns, their concatenation (alignments.concat_columns) and the samples' first
+                                 alignments; device_columns() / device_frag(): the upload, made once
+        lab0, n_labels, aln_sample   int64 [S + 1]; lab0[-1]; int32 device tensor [n_aln]: the sample of each alignment
+        labels, joined           int32 device tensors [n_aln] (assemble.extend_assemblies_many updates them in place)
+        rounds                   per sample the extension rounds its labels have been through; round_log: per sample one
+                                 (moved, unassigned before, new variants) per round (assemble.extend_assemblies_many)
+        names, keys              per sample what ContribReads.names and its keys would be
+        max_bytes                the budget of the assembly stage's tables (assign_reads_many)
+        sample(s)                an ordinary ContribReads over cols_list[s] with the sample's LOCAL labels, joined and rounds
+                                 (copies: changing it does not change the cohort): stats.report_contributors,
+                                 stats.write_statistics, assemble.write_consensus_seqs and as_dict work on it unchanged
+        label_of(s, name)        the global label of a name of sample s, or None
+        counts()                 alignments per global label, numpy int64 [n_labels]
+    """
+
+    def __init__(self, cols_list, cols, aln0, lab0, names, keys, labels, aln_sample, dcols=None, frag=None,
+                 max_bytes=COHORT_TABLES_BYTES):
+        self.cols_list, self.cols = list(cols_list), cols
+        self.aln0 = numpy.asarray(aln0, dtype=numpy.int64)
+        self.lab0 = numpy.asarray(lab0, dtype=numpy.int64)
+        self.n_samples, self.n_labels = len(self.cols_list), int(self.lab0[-1])
+        self.names = [list(n) for n in names]
+        self.keys = [list(k) for k in keys]
+        self.labels, self.aln_sample = labels, aln_sample
+        self.joined = torch.zeros(labels.numel(), dtype=torch.int32, device=labels.device)
+        self.rounds = [0] * self.n_samples
+        self.round_log = [[] for _ in range(self.n_samples)]
+        self.max_bytes = int(max_bytes)
+        self._dcols, self._frag = dcols, frag
+        self.n_frag = max(len(cols.names), int(cols.frag.max()) + 1 if len(cols) else 0)
+
+    def __len__(self):
+        return self.n_samples
+
+    def n_contribs(self, s):
+        return int(self.lab0[s + 1] - self.lab0[s]) - 1
+
+    def device_columns(self):
+        if self._dcols is None:
+            from .observe import DeviceColumns
+            self._dcols = DeviceColumns(self.cols, self.labels.device)
+        return self._dcols
+
+    def device_frag(self):
+        if self._frag is None:
+            self._frag = torch.from_numpy(numpy.ascontiguousarray(self.cols.frag, dtype=numpy.int64)).to(self.labels.device)
+        return self._frag
+
+    def label_of(self, s, name):
+        try:
+            return int(self.lab0[s]) + self.names[s].index(name)
+        except ValueError:
+            return None
+
+    def counts(self):
+        lab = self.labels[self.labels >= 0]
+        if not lab.numel():
+            return numpy.zeros(self.n_labels, dtype=numpy.int64)
+        return torch.bincount(lab.to(torch.int64), minlength=self.n_labels).cpu().numpy()
+
+    def sample(self, s):
+        s = int(s)
+        if not 0 <= s < self.n_samples:
+            raise IndexError("sample index out of range")
+        lo, hi = int(self.aln0[s]), int(self.aln0[s + 1])
+        glob = self.labels[lo:hi]
+        local = torch.where(glob >= 0, glob - int(self.lab0[s]), glob).to(torch.int32).contiguous()
+        cr = ContribReads(self.cols_list[s], local, self.names[s], self.keys[s])
+        cr.relabel(local, self.joined[lo:hi].clone())
+        cr.rounds = self.rounds[s]
+        return cr
+
+
+def assign_reads_many(cols_list, finished, reads_list, args, pileup=None, max_bytes=COHORT_TABLES_BYTES):
+    """
+    assign_reads for ALL samples of a cohort in one pass over the concatenated columns -> CohortContribReads.  Opt-in;
+    assign_reads is unchanged, and per sample the result is what assign_reads(cols_list[s], contribs, ...) gives: the same
+    label per alignment (.sample(s).labels), names and keys.
+    cols_list: the samples' alignments.AlignmentColumns; finished: assign.finish_many's list (contribs, assigned and
+    row_label are read); reads_list: the samples' rows of fragments (ReadIdGroups, or the reference's lists of read ids);
+    args: min_mq is read (the tables' length).
+    pileup: an observe.CohortPileup made with keep_columns=True over the same cols_list: its concatenated columns and their
+    upload are reused instead of uploading again.
+    The labels come from alignment_labels over the concatenated arrays (alignments.concat_columns re-bases the fragments, so
+    no two samples share one) and the global row labels of _cohort_label_plan: no kernel of its own.
+    max_bytes: the assembly stage that follows (assemble.extend_assemblies_many, call_consensus_many,
+    write_consensus_seqs_many) keeps one pileup table per global label, n_labels x L x 64 bytes (L: the longest pileup, at
+    least the reference's length); the non-strict consensus' tie rule takes the same size again as scratch.  Above
+    max_bytes -- default 4 GiB, a cap and not a measurement -- this function and those raise ValueError
+    ("... split the cohort"): nothing is chunked silently.
+    A sample without contributors has no names and no keys, and every alignment of it is labelled -1.
+    """
+    from .alignments import concat_columns
+    from .observe import pileup_length
+    cols_list = list(cols_list)
+    if not cols_list or len(finished) != len(cols_list) or len(reads_list) != len(cols_list):
+        raise ValueError("assign_reads_many: one finish_many result and one list of rows per sample are needed (%d samples, "
+                         "%d results, %d lists)" % (len(cols_list), len(finished), len(reads_list)))
+    n = len(cols_list)
+    lab0, names, keys, rows = _cohort_label_plan(finished, [len(reads) for reads in reads_list])
+    dcols = None
+    if pileup is not None and pileup.cols is not None:
+        joined, aln0, dcols = pileup.cols, pileup.aln0, pileup.dcols
+        if len(aln0) != n + 1 or any(int(aln0[s + 1] - aln0[s]) != len(c) for s, c in enumerate(cols_list)):
+            raise ValueError("assign_reads_many: the pileup's columns are not those of cols_list")
+    else:
+        joined, aln0 = concat_columns(cols_list)
+    _cohort_budget("assign_reads_many", int(lab0[-1]), pileup_length(joined, args.min_mq), max_bytes)
+    dev = require_gpu()
+    ptrs, groups, base, row0 = [numpy.zeros(1, dtype=numpy.int64)], [], 0, 0
+    for cols, reads in zip(cols_list, reads_list):
+        ptr, group_frag = _row_groups(cols, reads)
+        ptrs.append(ptr[1:] + row0)
+        groups.append(group_frag + base)
+        row0 += int(ptr[-1])
+        base += max(len(cols.names), int(cols.frag.max()) + 1 if len(cols) else 0)      # (concat_columns' re-basing)
+    frag_d = torch.from_numpy(numpy.ascontiguousarray(joined.frag, dtype=numpy.int64)).to(dev)
+    row_label = torch.from_numpy(numpy.concatenate(rows)).to(dev)
+    labels = alignment_labels(frag_d, torch.from_numpy(numpy.concatenate(ptrs)).to(dev),
+                              torch.from_numpy(numpy.concatenate(groups).astype(numpy.int64)).to(dev), row_label,
+                              max(base, 1))
+    aln_sample = torch.from_numpy(numpy.repeat(numpy.arange(n, dtype=numpy.int32), numpy.diff(aln0))).to(dev)
+    return CohortContribReads(cols_list, joined, aln0, lab0, names, keys, labels, aln_sample, dcols, frag_d, max_bytes)

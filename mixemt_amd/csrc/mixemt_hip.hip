@@ -36,6 +36,8 @@
 //   var_check_kernels.hpp  check_variants_samples_kernel (the variant check of a cohort's samples: assemble.py:157-208)
 //   assemble_kernels.hpp  consensus_kernel, new_variants_kernel, first_observed_kernel, extend_walk_kernel, extend_move_kernel
 //                       (consensus sequences and assembly extension over labelled pileups: assemble.py:431-585)
+//   assemble_samples_kernels.hpp  new_variants_samples_kernel, extend_walk_samples_kernel, extend_move_samples_kernel (a round
+//                       of the extension for the samples of a cohort over global labels)
 // This file: the host side of the C ABI (shape checks, grid sizing, dispatch, the loop drivers).  Every refusal goes
 // through fail / HIP_TRY / RC_TRY, a runtime chunk count reaches its kernel instance through dispatch_width<MAX>, the
 // checks several entry points share are dynamic_lds_ok, rest_check, coded_check, samples_check, records_lists_check.
@@ -79,6 +81,7 @@
 #include "observe_kernels.hpp"
 #include "var_check_kernels.hpp"
 #include "assemble_kernels.hpp"
+#include "assemble_samples_kernels.hpp"
 
 
 // ------------------------------------------------------------------------------------------
@@ -2887,4 +2890,120 @@ extern "C" int mxm_extend_assign(const mxm_aln_columns *cols, int32_t *label, in
     if (lds_refused) return -2;                              // (raise_dynamic_lds wrote the message)
     HIP_TRY(e);
     return aln_walk_error(name, err_host, "has a fragment index outside [0, n_frag)");
+}
+
+// ------------------------------------------------------------------------------------------
+// The extension for the samples of a cohort (assemble_samples_kernels.hpp; include/mixemt_hip_assemble_samples.h).  Every
+// refusal comes before the first HIP call.  The host tables go into stream-ordered memory of the call's own through a
+// pageable vector of the call's own, as mxm_check_variants_samples uploads its tables.
+// ------------------------------------------------------------------------------------------
+static_assert(ASM_MAX_USE == MXM_ASSEMBLE_SAMPLES_MAX_USE, "the header states the kernels' cap");
+
+// The participants' tables of S > 0 samples: use_ptr_host monotone from a start >= 0, at most ASM_MAX_USE entries per
+// sample, every entry in [0, limit).  *total = use_ptr_host[S], the entries of use_host that are uploaded.
+static int asm_samples_tables_ok(const char *name, const int32_t *use_host, const int32_t *use_ptr_host, int32_t S,
+                                 int64_t limit, int64_t *total) {
+    if (use_ptr_host == nullptr) return fail(-1, "%s: bad arguments (use_ptr_host is required)", name);
+    if (use_ptr_host[0] < 0) return fail(-1, "%s: use_ptr_host[0] = %d is negative", name, use_ptr_host[0]);
+    for (int32_t s = 0; s < S; ++s) {
+        const int32_t lo = use_ptr_host[s], hi = use_ptr_host[s + 1];
+        if (hi < lo) return fail(-1, "%s: use_ptr_host decreases at sample %d (%d after %d)", name, s, hi, lo);
+        if (hi - lo > ASM_MAX_USE)
+            return fail(-1, "%s: sample %d has %d participants, at most %d (an owner is an int8)", name, s, hi - lo, ASM_MAX_USE);
+    }
+    *total = use_ptr_host[S];
+    if (*total > 0 && use_host == nullptr) return fail(-1, "%s: bad arguments (use_host is required)", name);
+    for (int32_t s = 0; s < S; ++s)
+        for (int32_t k = use_ptr_host[s]; k < use_ptr_host[s + 1]; ++k)
+            if (use_host[k] < 0 || use_host[k] >= limit)
+                return fail(-1, "%s: sample %d: participant %d outside [0, %lld)", name, s, use_host[k], (long long)limit);
+    return 0;
+}
+
+extern "C" int mxm_new_variants_samples(const uint8_t *cons, int64_t ld, int32_t n_rows, const int32_t *use_host,
+                                        const int32_t *use_ptr_host, int32_t S, int64_t ref_len, uint32_t *newvar,
+                                        uint32_t *n_new, void *stream) {
+    const char *name = "mxm_new_variants_samples";
+    if (S < 0) return fail(-1, "%s: S < 0 (%d)", name, S);
+    if (ref_len < 0 || ld < ref_len || n_rows < 0)
+        return fail(-1, "%s: bad shape (ref_len = %lld, ld = %lld, n_rows = %d)", name, (long long)ref_len, (long long)ld, n_rows);
+    if (S == 0) return 0;
+    int64_t total = 0;
+    RC_TRY(asm_samples_tables_ok(name, use_host, use_ptr_host, S, n_rows, &total));
+    if (ref_len == 0 || use_ptr_host[S] == use_ptr_host[0]) return 0;
+    if (cons == nullptr || newvar == nullptr || n_new == nullptr)
+        return fail(-1, "%s: bad arguments (cons, newvar and n_new are required)", name);
+    hipStream_t st = (hipStream_t)stream;
+    // use_ptr[S + 1], then use[total]
+    static thread_local std::vector<int32_t> staged;
+    staged.assign(use_ptr_host, use_ptr_host + (size_t)S + 1);
+    staged.insert(staged.end(), use_host, use_host + (size_t)total);
+    int32_t *tables = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void **>(&tables), staged.size() * sizeof(int32_t), st));
+    hipError_t e = hipMemcpyAsync(tables, staged.data(), staged.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        const int gx = clamp_grid((ref_len + ASM_THREADS - 1) / ASM_THREADS, num_cu() * 8);
+        hipLaunchKernelGGL(new_variants_samples_kernel, dim3((unsigned)gx, (unsigned)(S < 65535 ? S : 65535)), dim3(ASM_THREADS),
+                           0, st, cons, ld, (const int32_t *)(tables + S + 1), (const int32_t *)tables, S, ref_len, newvar, n_new);
+        e = hipGetLastError();
+    }
+    const hipError_t ef = hipFreeAsync(tables, st);
+    HIP_TRY(e);
+    HIP_TRY(ef);
+    return 0;
+}
+
+extern "C" int mxm_extend_assign_samples(const mxm_aln_columns *cols, const int32_t *aln_sample, int32_t *label,
+                                         int32_t *joined, const int32_t *unassigned_host, const int32_t *use_host,
+                                         const int32_t *use_ptr_host, int32_t S, int32_t n_labels, int32_t round,
+                                         int32_t min_mq, int32_t min_bq, const uint32_t *newvar, int64_t ref_len,
+                                         int32_t *frag_state, int32_t *moved_owner, uint32_t *n_moved, void *stream) {
+    const char *name = "mxm_extend_assign_samples";
+    RC_TRY(aln_columns_ok(name, cols));
+    if (S < 0) return fail(-1, "%s: S < 0 (%d)", name, S);
+    if (n_labels < 0 || ref_len < 0 || cols->n_frag < 0 || round < 0)
+        return fail(-1, "%s: bad shape (n_labels = %d, ref_len = %lld, n_frag = %lld, round = %d)", name, n_labels,
+                    (long long)ref_len, (long long)cols->n_frag, round);
+    int64_t total = 0;
+    const int32_t zero = 0;
+    if (S > 0) {
+        if (unassigned_host == nullptr) return fail(-1, "%s: bad arguments (unassigned_host is required)", name);
+        RC_TRY(asm_samples_tables_ok(name, use_host, use_ptr_host, S, n_labels, &total));
+        for (int32_t s = 0; s < S; ++s)
+            if (unassigned_host[s] >= n_labels)
+                return fail(-1, "%s: sample %d: unassigned label %d outside [0, %d)", name, s, unassigned_host[s], n_labels);
+    } else {
+        use_ptr_host = &zero;                                // (no sample: one offset, no entries)
+    }
+    const int64_t n = cols->n_aln, n_frag = cols->n_frag;
+    if (n == 0) return 0;
+    if (label == nullptr || joined == nullptr || cols->frag == nullptr || aln_sample == nullptr || n_moved == nullptr ||
+        (n_frag > 0 && frag_state == nullptr) || (S > 0 && ref_len > 0 && newvar == nullptr))
+        return fail(-1, "%s: bad arguments (label, joined, frag, aln_sample, frag_state, newvar and n_moved are required)", name);
+    hipStream_t s = (hipStream_t)stream;
+    // the tables as one upload: unassigned[S], use_ptr[S + 1], use[total]
+    static thread_local std::vector<int32_t> staged;
+    staged.assign(unassigned_host, unassigned_host + (size_t)S);
+    staged.insert(staged.end(), use_ptr_host, use_ptr_host + (size_t)S + 1);
+    staged.insert(staged.end(), use_host, use_host + (size_t)total);
+    unsigned long long err_host;
+    const size_t bytes = staged.size() * sizeof(int32_t);
+    HIP_TRY(aln_pass(s, bytes, &err_host, [&](void *scratch, unsigned long long *err) {
+        int32_t *un_d = static_cast<int32_t *>(scratch), *ptr_d = un_d + S, *use_d = ptr_d + S + 1;
+        hipError_t st = hipMemcpyAsync(un_d, staged.data(), bytes, hipMemcpyHostToDevice, s);
+        if (st == hipSuccess && n_frag > 0) st = hipMemsetAsync(frag_state, 0xff, (size_t)n_frag * 4, s);   // ASM_FRAG_EMPTY
+        if (st != hipSuccess) return st;
+        hipLaunchKernelGGL(extend_walk_samples_kernel, dim3(clamp_grid(((n + 63) / 64 + 7) / 8, num_cu() * 4)),
+                           dim3(ASM_WALK_THREADS), 0, s, aln_view_of(cols, min_mq, min_bq), cols->frag, (const int32_t *)label,
+                           aln_sample, S, (const int32_t *)un_d, (const int32_t *)use_d, (const int32_t *)ptr_d, n_frag, newvar,
+                           ref_len, frag_state, err);
+        hipLaunchKernelGGL(extend_move_samples_kernel, dim3(clamp_grid((n + ASM_THREADS - 1) / ASM_THREADS, num_cu() * 8)),
+                           dim3(ASM_THREADS), 0, s, cols->frag, n, n_frag, aln_sample, S, (const int32_t *)un_d,
+                           (const int32_t *)use_d, (const int32_t *)ptr_d, round, (const int32_t *)frag_state, label, joined,
+                           moved_owner, n_moved);
+        return hipGetLastError();
+    }));
+    char kind0[64];
+    snprintf(kind0, sizeof(kind0), "has a sample outside [0, %d)", S);
+    return aln_walk_error(name, err_host, "has a fragment index outside [0, n_frag)", kind0);
 }

@@ -150,6 +150,9 @@ class CohortPileup(object):
         host(s)           an ObservedBases over a host copy of table s (downloaded on first use, cached): every query
                           answers as observe_bases(cols_list[s]) does -- a position past the sample's own length has no
                           observations in either
+        cols, dcols, aln0 None, or with observe_bases_many(keep_columns=True) the concatenated AlignmentColumns, their
+                          DeviceColumns and the samples' first alignments (alignments.concat_columns): the upload kept for
+                          assign.assign_reads_many
     """
 
     def __init__(self, counts, lengths, min_mq=30, min_bq=30):
@@ -158,6 +161,7 @@ class CohortPileup(object):
         self.lengths = [int(n) for n in lengths]
         self.min_map_qual, self.min_base_qual = min_mq, min_bq
         self.upload_s = 0.0
+        self.cols = self.dcols = self.aln0 = None
         self._host = {}
 
     def __len__(self):
@@ -174,12 +178,14 @@ class CohortPileup(object):
         return got
 
 
-def observe_bases_many(cols_list, min_mq=30, min_bq=30, ref_len=None, max_bytes=COHORT_PILEUP_BYTES):
+def observe_bases_many(cols_list, min_mq=30, min_bq=30, ref_len=None, max_bytes=COHORT_PILEUP_BYTES, keep_columns=False):
     """
     observe_bases for the samples of a cohort in one upload and ONE labelled pileup call (the label of an alignment is
     its sample): -> CohortPileup with counts [S][L][16], L = the largest pileup_length among the samples.  The table takes
     S * L * 64 bytes (272 MB for 256 samples at L = 16 589); above max_bytes (default 1 GiB) this raises ValueError and
     the caller splits the cohort -- nothing is chunked silently.
+    keep_columns: the returned pileup also carries the concatenated columns, their upload and aln0 (CohortPileup.cols /
+    .dcols / .aln0), so that assign.assign_reads_many does not upload again; by default the upload is freed with the call.
     """
     from .alignments import concat_columns
     cols_list = list(cols_list)
@@ -200,6 +206,8 @@ def observe_bases_many(cols_list, min_mq=30, min_bq=30, ref_len=None, max_bytes=
         count_bases_labelled(dcols, label, counts, min_mq, min_bq)
     pileup = CohortPileup(counts, lengths, min_mq, min_bq)
     pileup.upload_s = dcols.upload_s
+    if keep_columns:
+        pileup.cols, pileup.dcols, pileup.aln0 = joined, dcols, aln0
     return pileup
 
 
