@@ -229,10 +229,13 @@ int mxm_linearize(const double *M, int64_t ldm, int64_t R, int32_t H,
  * Restarts with state[b].done != 0 are skipped (their colsum is left untouched).
  * A row with Z_b[r] == 0 (-inf in every column) and w[r] != 0 makes every T_bh NaN, as the
  * reference's -inf - (-inf) does (em.py:81-83, :87); with w[r] == 0 it is dropped like scipy drops it.
- * LIMIT of the linear form: Z_b[r] is also 0 when every haplogroup that supports row r (P > 0) has a
+ * LIMIT of every form of this pass: Z_b[r] is also 0 when every haplogroup that supports row r (P > 0) has a
  * proportion whose exp() underflowed (ln p < -745) although the row is not empty; the reference's
  * log-space E-step stays finite there, this kernel poisons the restart with NaN (it then runs to
- * max_iter and reports NaN proportions -- loud, not silent).  Matrices from build_em_matrix cannot
+ * max_iter and reports NaN proportions -- loud, not silent).  That includes the kernels that stream M (H <= 64,
+ * H > 8192): they shift a row by the maximum of M[r][:], not of ln p + M[r][:], so exp(ln p_h + M[r][h] - max) is
+ * 0 for such a row all the same (tests/test_gpu_accuracy_loops.py, the last test); only the posterior passes
+ * (mxm_em_step, mxm_em_step_coded) follow the reference into that regime.  Matrices from build_em_matrix cannot
  * get there: every cell is finite and >= k * log(0.0033), so the best-supported haplogroup of a row
  * keeps P = 1 and would need ln p < -745 while the row's weight pulls it up every iteration.
  * props[B][H] = exp(ln_props[B][H]) (theta_k), w[R] fp64 weights (NULL = all 1).

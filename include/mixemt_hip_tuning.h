@@ -94,6 +94,15 @@ int mxm_set_loop_graph(int32_t mode);
  * (same bits: a resumed restart continues from its saved proportions); 0 = one launch.
  * Against the per-iteration kernels the results differ by rounding only (another summation
  * order; the linear proportions are carried as p T / tot instead of exp(ln p')).
+ * LIMIT of the carried proportions: the log state is exact at any depth, but a linear proportion that has become
+ * subnormal (ln p < -708.4) has lost mantissa bits the product p T / tot never gets back, and one that has reached 0
+ * (ln p < -745.1) stays 0 -- it is not re-derived from its log, as mxm_m_finalize's exp(ln_new) is.  While such a
+ * proportion stays down there it weighs less than 2^-1022 of any Z_r and ln_new is inside the accuracy rule
+ * (tests/test_gpu_accuracy_loops.py: 40 iterations with half the proportions subnormal or zero); props_cur then holds
+ * the carried value (measured there: up to 100 % off exp(ln_cur) for proportions that had been subnormal, a few u for
+ * all others).  A proportion that CLIMBS BACK from below 1e-308 to a visible size would enter the sums with that error,
+ * or not at all: a run in which that can happen (it needs a haplogroup whose log proportion rises by hundreds) belongs
+ * to the per-iteration kernels, mxm_set_loop_fused(0, 0).
  */
 int mxm_set_loop_fused(int32_t mode, int32_t chunk);
 

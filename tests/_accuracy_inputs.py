@@ -12,7 +12,10 @@ where kernels go wrong.  Everything comes from oracle/, mixemt_amd.synth and num
   * weights: integers 1 .. 4 plus one zero weight;
   * two proportion vectors per matrix: "dirichlet" = rng.dirichlet([1] * H), and "skewed", the converged regime:
     ln p ~ U(-250, -5), then ln p[[0, H // 2]] = log([0.6, 0.3]) and ln p[H - 1] = log(1e-12).  Nothing is normalised:
-    the kernels take any positive vector, and so does the reference.
+    the kernels take any positive vector, and so does the reference;
+  * the LOOP tests (tests/test_exact_traj.py, tests/test_gpu_accuracy_loops.py): 96-row matrices (loop_matrix) and a third
+    vector, "deep" (deep_vector): ln p ~ U(-760, -690) around the skewed vector's three entries, i.e. proportions that are
+    subnormal or zero in linear space.
 """
 import numpy
 
@@ -85,6 +88,45 @@ def prop_vectors(n_haps, seed=0):
     ln[[0, n_haps // 2]] = numpy.log([0.6, 0.3])
     ln[n_haps - 1] = numpy.log(1e-12)
     return {"dirichlet": (p, numpy.log(p)), "skewed": (numpy.exp(ln), ln)}
+
+
+def deep_vector(n_haps, seed=0, head=(0.6, 0.3)):
+    """"deep" (props, ln_props), the regime every long run ends in: ln p ~ U(-760, -690), then the three entries of the
+    skewed vector -- about half the proportions are subnormal in fp64 (ln p < -708.4), a fifth are zero (ln p < -745.1),
+    and more cross either line while a loop runs (tests/test_exact_traj.py prints the counts).  A generator of its own:
+    prop_vectors' draws stay what they were."""
+    rng = numpy.random.default_rng(7700 + seed + n_haps)
+    ln = rng.uniform(-760.0, -690.0, size=n_haps)
+    ln[[0, n_haps // 2]] = numpy.log(head)             # (another head: a restart that takes another way, and stops elsewhere)
+    ln[n_haps - 1] = numpy.log(1e-12)
+    return numpy.exp(ln), ln
+
+
+LOOP_ROWS = 96
+LOOP_WIDTHS_REAL = (66, 1025, 5408)
+LOOP_WIDTHS_LOG = (3, 16, 17, 64, 8200)         # (16: the widest instance of the narrow one-launch loop)
+LOOP_STEPS = (2, 3, 10, 40)
+
+
+def loop_matrix(b17, n_haps):
+    """(label, log matrix, weights) of the loop tests: 96 rows -- the first 93 reads and the three 4000-bp rows at the real
+    widths (from 63 rows on the one-launch records loop takes Build 17's width itself), few-values rows at the log-space
+    widths."""
+    if n_haps in LOOP_WIDTHS_REAL:
+        reads = real_rows(b17, n_haps, "reads")
+        mat, label = numpy.concatenate([reads[:LOOP_ROWS - N_LONG], reads[N_READS:]]), "reads[:93] + long"
+    else:
+        mat, label = few_values(LOOP_ROWS, n_haps), "few values"
+    assert mat.shape == (LOOP_ROWS, n_haps)
+    return "%s %d" % (label, n_haps), numpy.array(mat), weights(LOOP_ROWS)
+
+
+def loop_vectors(n_haps):
+    """{name: (props, ln_props)}: the two existing vectors, and "deep" where the width leaves it entries of its own."""
+    vecs = dict(prop_vectors(n_haps))
+    if n_haps >= 16:
+        vecs["deep"] = deep_vector(n_haps)
+    return vecs
 
 
 def linearise(mat):

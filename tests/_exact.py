@@ -52,7 +52,7 @@ def _props2d(props):
 
 def exact_colsum(P, props, w):
     """T[B][H] (long double) from the linearised matrix P[R][H] (fp64 or fp32 bits), props[B][H] or [H], w[R]."""
-    P = numpy.asarray(P).astype(LD)
+    P = numpy.asarray(P).astype(LD, copy=False)         # (a long-double matrix is taken as it is: the trajectory's K passes)
     w = numpy.asarray(w).astype(LD)
     p2 = _props2d(props)
     out = numpy.empty((p2.shape[0], P.shape[1]), dtype=LD)

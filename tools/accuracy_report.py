@@ -1,8 +1,10 @@
 #!/usr/bin/env python
 """
-profiles/accuracy/README.md from a run of tests/test_gpu_accuracy.py on the GPU: the module writes the figures it measured
-(per form, width, rows and proportion vector: the kernel's error against the extended-precision reference, the sequential
-fp64 pass's, their ratio, the loops' ln_new error) as a table; this wraps it with the text that explains the columns.
+profiles/accuracy/README.md from a run of tests/test_gpu_accuracy.py and tests/test_gpu_accuracy_loops.py on the GPU: the
+modules write the figures they measured -- one pass per form (the kernel's error against the extended-precision reference,
+the sequential fp64 pass's, their ratio, the loops' ln_new error), and every loop form over K = 2, 3, 10 and 40 iterations
+(the error of ln_new in units of K u max(1, max |ln|), beside the comparison pass's) -- as tables; this wraps them with the text
+that explains the columns.
     python tools/accuracy_report.py [output.md [more pytest arguments]]
 """
 import os
@@ -12,7 +14,8 @@ import sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEAD = """# Accuracy of the EM passes against an extended-precision reference
 
-Written by `tools/accuracy_report.py` from `pytest -m gpu tests/test_gpu_accuracy.py` (MI355X).  One pass per form; `T` is
+Written by `tools/accuracy_report.py` from `pytest -m gpu tests/test_gpu_accuracy.py tests/test_gpu_accuracy_loops.py`
+(MI355X).  One pass per form; `T` is
 `colsum`, the M-step sums without their factor `p_h`; `u = 2^-53`; `rel(X) = max_h |X_h - T_exact,h| / T_exact,h` with
 `T_exact` from `tests/_exact.py` (numpy.longdouble on the bits the kernel reads).  `T_seq` is a plain fp64 pass in
 sequential order on the same inputs (for the log-space forms: `oracle.em_oracle.em_step`).  The tests assert
@@ -21,19 +24,33 @@ asserted `<= 8 * max(the fp64 oracle's own error, u * max |value|)`.  The one-la
 carry the `ln_new` error only.
 
 """
+LOOPS = """
+# The loops over K iterations
+
+`tests/test_gpu_accuracy_loops.py`: every loop form run for K = 2, 3, 10 and 40 iterations (`tol = 0`) from the vectors
+"dirichlet", "skewed" and "deep" (`ln p ~ U(-760, -690)`: subnormal or zero in linear space) on 96-row matrices, against
+the long-double trajectory of `tests/_exact_traj.py`.  Each cell is `max_h |ln_new - ln_exact,K|` of the loop and of the
+comparison pass (the same recurrence in plain fp64), both in units of the floor `K u max(1, max_h |ln_exact,K|)`; the test asserts
+`error <= 8 * max(comparison pass, floor)`.
+
+"""
 
 
 def main():
     out = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "accuracy", "README.md")
     table = out + ".table"
     env = dict(os.environ, MXM_ACCURACY_REPORT=table)
-    rc = subprocess.call([sys.executable, "-m", "pytest", "-m", "gpu", "-q", os.path.join(ROOT, "tests", "test_gpu_accuracy.py")] + sys.argv[2:],
-                         cwd=ROOT, env=env)
-    if os.path.exists(table):
-        if rc == 0:                                    # (a failed or interrupted run leaves the committed table alone)
-            with open(table) as src, open(out, "w") as dst:
-                dst.write(HEAD + src.read())
-        os.remove(table)
+    rc = subprocess.call([sys.executable, "-m", "pytest", "-m", "gpu", "-q", os.path.join(ROOT, "tests", "test_gpu_accuracy.py"),
+                          os.path.join(ROOT, "tests", "test_gpu_accuracy_loops.py")] + sys.argv[2:], cwd=ROOT, env=env)
+    parts = [table, table + ".loops"]
+    if all(os.path.exists(p) for p in parts) and rc == 0:          # (a failed or interrupted run leaves the committed tables alone)
+        with open(out, "w") as dst:
+            for head, part in zip((HEAD, LOOPS), parts):
+                with open(part) as src:
+                    dst.write(head + src.read())
+    for part in parts:
+        if os.path.exists(part):
+            os.remove(part)
     return rc
 
 
