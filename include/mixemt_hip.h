@@ -790,4 +790,6 @@ void mxm_exchange_destroy(mxm_exchange *x);
 #include "mixemt_hip_var_check.h"
 /* the assembly extension for the samples of a cohort: new variants and the walk + move over global labels */
 #include "mixemt_hip_assemble_samples.h"
+/* mixemt's -t tables of a cohort's samples as text, formatted on the device */
+#include "mixemt_hip_stats_samples.h"
 #endif /* MIXEMT_HIP_H */

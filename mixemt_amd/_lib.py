@@ -214,6 +214,20 @@ ASSEMBLE_SAMPLES_SIGNATURES = {
                                                  c_i32, c_i32, c_i32, c_i32, c_ptr, c_i64, c_ptr, c_ptr, c_ptr, c_ptr]),
 }
 
+class StatsText(ctypes.Structure):
+    """mxm_stats_text (include/mixemt_hip_stats_samples.h): text blocks over pileup tables (a host struct)."""
+    _fields_ = [("kind", c_i32), ("n_blocks", c_i32), ("n_pos", c_i64), ("table_host", c_ptr), ("prefix_host", c_ptr),
+                ("prefix_ptr_host", c_ptr), ("poly", c_ptr), ("thr", c_ptr), ("tail", c_ptr), ("tail_ptr", c_ptr)]
+
+
+# mixemt's -t tables of a cohort's samples formatted on the device (include/mixemt_hip_stats_samples.h: additions behind ABI
+# version 603); their refusals are pinned in tests/test_stats_samples_host.py
+STATS_SAMPLES_SIGNATURES = {
+    "mxm_stats_text_tiles": (c_i64, [c_i32, c_i64]),
+    "mxm_stats_text_sizes": (ctypes.c_int, [ctypes.POINTER(StatsText), c_ptr, c_ptr]),
+    "mxm_stats_text_write": (ctypes.c_int, [ctypes.POINTER(StatsText), c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
+}
+
 # the MXM_VERSION of include/mixemt_hip.h these signatures were written for; load() refuses any other
 ABI_VERSION = 603
 
@@ -251,7 +265,8 @@ def load():
         raise MixemtHipError("%s reports ABI version %s, this binding was written for %d: rebuild with "
                              "`python -m mixemt_amd.build --force`" % (LIB_PATH, have, ABI_VERSION))
     for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(FINISH_SIGNATURES.items())
-                                      + list(VARCHECK_SIGNATURES.items()) + list(ASSEMBLE_SAMPLES_SIGNATURES.items())):
+                                      + list(VARCHECK_SIGNATURES.items()) + list(ASSEMBLE_SAMPLES_SIGNATURES.items())
+                                      + list(STATS_SAMPLES_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:

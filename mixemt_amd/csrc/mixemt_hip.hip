@@ -38,6 +38,8 @@
 //                       (consensus sequences and assembly extension over labelled pileups: assemble.py:431-585)
 //   assemble_samples_kernels.hpp  new_variants_samples_kernel, extend_walk_samples_kernel, extend_move_samples_kernel (a round
 //                       of the extension for the samples of a cohort over global labels)
+//   stats_text_kernels.hpp  stats_text_sizes_kernel, stats_text_scan_kernel, stats_text_write_kernel (mixemt's -t tables as
+//                       text: a tile of 256 lines per workgroup, digits by integer arithmetic)
 // This file: the host side of the C ABI (shape checks, grid sizing, dispatch, the loop drivers).  Every refusal goes
 // through fail / HIP_TRY / RC_TRY, a runtime chunk count reaches its kernel instance through dispatch_width<MAX>, the
 // checks several entry points share are dynamic_lds_ok, rest_check, coded_check, samples_check, records_lists_check.
@@ -82,6 +84,7 @@
 #include "var_check_kernels.hpp"
 #include "assemble_kernels.hpp"
 #include "assemble_samples_kernels.hpp"
+#include "stats_text_kernels.hpp"
 
 
 // ------------------------------------------------------------------------------------------
@@ -3006,4 +3009,122 @@ extern "C" int mxm_extend_assign_samples(const mxm_aln_columns *cols, const int3
     char kind0[64];
     snprintf(kind0, sizeof(kind0), "has a sample outside [0, %d)", S);
     return aln_walk_error(name, err_host, "has a fragment index outside [0, n_frag)", kind0);
+}
+
+// ------------------------------------------------------------------------------------------
+// mixemt's -t tables as text (stats_text_kernels.hpp; include/mixemt_hip_stats_samples.h).  Every refusal comes before the
+// first HIP call.  The host tables go into stream-ordered memory of the call's own through a pageable vector of the call's
+// own, as mxm_new_variants_samples uploads its tables.
+// ------------------------------------------------------------------------------------------
+static_assert(STATS_TILE == MXM_STATS_TILE_LINES && STATS_MAX_PREFIX == MXM_STATS_MAX_PREFIX, "the header states the kernels' sizes");
+
+static int64_t stats_tiles_per_block(int64_t n_pos) { return (n_pos + STATS_TILE - 1) / STATS_TILE; }
+
+extern "C" int64_t mxm_stats_text_tiles(int32_t n_blocks, int64_t n_pos) {
+    if (n_blocks < 0 || n_pos < 0 || n_pos > (int64_t)INT32_MAX - 1) return -1;
+    const int64_t tiles = (int64_t)n_blocks * stats_tiles_per_block(n_pos);
+    return tiles > (int64_t)INT32_MAX ? -1 : tiles;
+}
+
+// The checks both entries share; *n_tiles: the tiles of the text (0: nothing to do).
+static int stats_text_ok(const char *name, const mxm_stats_text *t, int64_t *n_tiles) {
+    if (t == nullptr) return fail(-1, "%s: bad arguments (the mxm_stats_text is required)", name);
+    if (t->n_blocks < 0 || t->n_pos < 0)
+        return fail(-1, "%s: bad shape (n_blocks = %d, n_pos = %lld)", name, t->n_blocks, (long long)t->n_pos);
+    if (t->kind != 0 && t->kind != 1) return fail(-1, "%s: unknown kind %d (0: obs.tab lines, 1: pos.tab lines)", name, t->kind);
+    *n_tiles = mxm_stats_text_tiles(t->n_blocks, t->n_pos);
+    if (*n_tiles < 0)
+        return fail(-1, "%s: %d blocks of %lld lines are more than the tile index holds (n_pos <= 2^31 - 2, at most 2^31 - 1 "
+                        "tiles of %d lines)", name, t->n_blocks, (long long)t->n_pos, STATS_TILE);
+    if (*n_tiles == 0) return 0;
+    if (t->table_host == nullptr) return fail(-1, "%s: bad arguments (table_host is required)", name);
+    for (int32_t b = 0; b < t->n_blocks; ++b)
+        if (((uintptr_t)t->table_host[b] & 15) != 0) return fail(-1, "%s: the table of block %d is not 16-byte aligned", name, b);
+    if (t->kind == 0) {
+        const int64_t *ptr = t->prefix_ptr_host;
+        if (ptr == nullptr) return fail(-1, "%s: bad arguments (prefix_ptr_host is required)", name);
+        if (ptr[0] < 0) return fail(-1, "%s: prefix_ptr_host[0] = %lld is negative", name, (long long)ptr[0]);
+        for (int32_t b = 0; b < t->n_blocks; ++b) {
+            if (ptr[b + 1] < ptr[b])
+                return fail(-1, "%s: prefix_ptr_host decreases at block %d (%lld after %lld)", name, b, (long long)ptr[b + 1],
+                            (long long)ptr[b]);
+            if (ptr[b + 1] - ptr[b] > STATS_MAX_PREFIX)
+                return fail(-1, "%s: block %d has a prefix of %lld bytes, at most %d (the lines are staged in LDS)", name, b,
+                            (long long)(ptr[b + 1] - ptr[b]), STATS_MAX_PREFIX);
+        }
+        if (ptr[t->n_blocks] > ptr[0] && t->prefix_host == nullptr)
+            return fail(-1, "%s: bad arguments (prefix_host is required)", name);
+    } else if (t->poly == nullptr || t->thr == nullptr || t->tail_ptr == nullptr) {
+        return fail(-1, "%s: bad arguments (poly, thr and tail_ptr are required)", name);
+    }
+    return 0;
+}
+
+// The host tables as ONE upload: table[n_blocks] pointers, then (kind 0) prefix_ptr[n_blocks + 1] re-based to 0 and the
+// prefixes' bytes.  `f` enqueues the kernels over the view; the tables are freed behind them in stream order.
+template <typename F>
+static int stats_text_launch(const mxm_stats_text *t, hipStream_t st, F &&f) {
+    static thread_local std::vector<uint64_t> staged;
+    const size_t nb = (size_t)t->n_blocks;
+    staged.assign(nb, 0);
+    for (size_t b = 0; b < nb; ++b) staged[b] = (uint64_t)(uintptr_t)t->table_host[b];
+    size_t prefix_bytes = 0;
+    if (t->kind == 0) {
+        const int64_t lo = t->prefix_ptr_host[0];
+        prefix_bytes = (size_t)(t->prefix_ptr_host[nb] - lo);
+        for (size_t b = 0; b <= nb; ++b) staged.push_back((uint64_t)(t->prefix_ptr_host[b] - lo));
+        staged.resize(staged.size() + (prefix_bytes + 7) / 8, 0);
+        if (prefix_bytes) memcpy(staged.data() + 2 * nb + 1, t->prefix_host + lo, prefix_bytes);
+    }
+    uint64_t *tables = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void **>(&tables), staged.size() * sizeof(uint64_t), st));
+    hipError_t e = hipMemcpyAsync(tables, staged.data(), staged.size() * sizeof(uint64_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        stats_text_view v;
+        v.kind = t->kind, v.n_blocks = t->n_blocks, v.n_pos = t->n_pos;
+        v.tiles_per_block = (int32_t)stats_tiles_per_block(t->n_pos);
+        v.table = reinterpret_cast<const uint32_t *const *>(tables);
+        v.prefix_ptr = t->kind == 0 ? reinterpret_cast<const int64_t *>(tables + nb) : nullptr;
+        v.prefix = t->kind == 0 ? reinterpret_cast<const uint8_t *>(tables + 2 * nb + 1) : nullptr;
+        v.poly = t->poly, v.thr = t->thr, v.tail = t->tail, v.tail_ptr = t->tail_ptr;
+        f(v);
+        e = hipGetLastError();
+    }
+    const hipError_t ef = hipFreeAsync(tables, st);
+    HIP_TRY(e);
+    HIP_TRY(ef);
+    return 0;
+}
+
+extern "C" int mxm_stats_text_sizes(const mxm_stats_text *t, int64_t *tile_off, void *stream) {
+    const char *name = "mxm_stats_text_sizes";
+    int64_t n_tiles = 0;
+    RC_TRY(stats_text_ok(name, t, &n_tiles));
+    if (tile_off == nullptr) return fail(-1, "%s: bad arguments (tile_off is required)", name);
+    hipStream_t st = (hipStream_t)stream;
+    if (n_tiles == 0) {
+        HIP_TRY(hipMemsetAsync(tile_off, 0, sizeof(int64_t), st));
+        return 0;
+    }
+    return stats_text_launch(t, st, [&](const stats_text_view &v) {
+        hipLaunchKernelGGL(stats_text_sizes_kernel, dim3(clamp_grid(n_tiles, num_cu() * 32)), dim3(STATS_TILE), 0, st, v, n_tiles,
+                           tile_off);
+        hipLaunchKernelGGL(stats_text_scan_kernel, dim3(1), dim3(STATS_SCAN_THREADS), 0, st, tile_off, n_tiles);
+    });
+}
+
+extern "C" int mxm_stats_text_write(const mxm_stats_text *t, const int64_t *tile_off, uint8_t *out, int64_t out_bytes,
+                                    uint32_t *err, void *stream) {
+    const char *name = "mxm_stats_text_write";
+    int64_t n_tiles = 0;
+    RC_TRY(stats_text_ok(name, t, &n_tiles));
+    if (out_bytes < 0) return fail(-1, "%s: out_bytes < 0 (%lld)", name, (long long)out_bytes);
+    if (out == nullptr && out_bytes > 0) return fail(-1, "%s: bad arguments (out is NULL with out_bytes = %lld)", name, (long long)out_bytes);
+    if (tile_off == nullptr || err == nullptr) return fail(-1, "%s: bad arguments (tile_off and err are required)", name);
+    if (n_tiles == 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+    return stats_text_launch(t, st, [&](const stats_text_view &v) {
+        hipLaunchKernelGGL(stats_text_write_kernel, dim3(clamp_grid(n_tiles, num_cu() * 32)), dim3(STATS_TILE), 0, st, v, n_tiles,
+                           tile_off, out, out_bytes, err);
+    });
 }
