@@ -792,4 +792,5 @@ void mxm_exchange_destroy(mxm_exchange *x);
 #include "mixemt_hip_assemble_samples.h"
 /* mixemt's -t tables of a cohort's samples as text, formatted on the device */
 #include "mixemt_hip_stats_samples.h"
+#include "mixemt_hip_samples_runs.h"
 #endif /* MIXEMT_HIP_H */

@@ -228,6 +228,20 @@ STATS_SAMPLES_SIGNATURES = {
     "mxm_stats_text_write": (ctypes.c_int, [ctypes.POINTER(StatsText), c_ptr, c_ptr, c_i64, c_ptr, c_ptr]),
 }
 
+# the batched second half for samples of several EM runs (include/mixemt_hip_samples_runs.h: additions behind ABI version 603);
+# their refusals are pinned in tests/test_samples_runs_host.py
+SAMPLES_RUNS_SIGNATURES = {
+    "mxm_samples_runs_workspace_bytes": (c_size, [c_i64, c_i32, c_i32, c_i32]),
+    "mxm_votes_samples_runs": (ctypes.c_int, [ctypes.POINTER(Coded), c_ptr, c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr,
+                                              c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+    "mxm_em_loop_samples_narrow_runs": (ctypes.c_int, [ctypes.POINTER(Coded), c_ptr, c_i32, c_i32, c_i32, c_ptr, c_i32, c_ptr,
+                                                       c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f64, c_i32, c_i32, c_ptr, c_ptr,
+                                                       c_size, c_ptr, ctypes.POINTER(EmState)]),
+    "mxm_assign_reads_samples_runs": (ctypes.c_int, [ctypes.POINTER(Coded), c_ptr, c_i32, c_i32, c_i32, c_ptr, c_i32, c_ptr,
+                                                     c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f64, c_ptr, c_ptr, c_ptr, c_size,
+                                                     c_ptr]),
+}
+
 # the MXM_VERSION of include/mixemt_hip.h these signatures were written for; load() refuses any other
 ABI_VERSION = 603
 
@@ -266,7 +280,7 @@ def load():
                              "`python -m mixemt_amd.build --force`" % (LIB_PATH, have, ABI_VERSION))
     for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(FINISH_SIGNATURES.items())
                                       + list(VARCHECK_SIGNATURES.items()) + list(ASSEMBLE_SAMPLES_SIGNATURES.items())
-                                      + list(STATS_SAMPLES_SIGNATURES.items())):
+                                      + list(STATS_SAMPLES_SIGNATURES.items()) + list(SAMPLES_RUNS_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:

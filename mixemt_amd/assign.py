@@ -625,15 +625,21 @@ def check_variants_samples(counts, tables, cands, args, want_counts=False):
 FINISH_KMAX = 16                    # contributors a batched sample may have (the reduced matrix's widest row stride)
 FINISH_MAX_ROWS = 100000            # rows up to which one workgroup per sample was measured not slower than the per-sample
                                     # refinement (S = 64: 0.10 / 0.15 / 0.44 / 1.00 of the per-sample loop's wall time at 600 /
-                                    # 4 600 / 3 * 10^4 / 10^5 rows, profiles/samples/finish.md); nothing larger was measured
+                                    # 4 600 / 3 * 10^4 / 10^5 rows, profiles/samples/finish.md); nothing larger was measured.
+                                    # Measured for ONE run per sample only: finish_many(runs="batch") shares the limit
+                                    # (profiles/samples/runs.md)
+FINISH_RUNS_MAX = 64                # runs per sample the batch route takes with runs="batch" (MXM_SAMPLES_RUNS_MAX: a cap)
 
 
-def _finish_route(n_rows, first_route, n_multi, max_rows, n_contribs=None, n_columns=None):
+def _finish_route(n_rows, first_route, n_multi, max_rows, n_contribs=None, n_columns=None, runs="single"):
     """'batch' or 'single' for one sample of finish_many: the per-sample functions take a sample whose first EM ran on
-    its own, every sample of a multi-run (the fold of the runs' posteriors, em.py:156, is theirs), one of more than
-    max_rows rows, and -- once its contributors are known -- one with more than FINISH_KMAX of them (or with a
-    haplogroup named twice, whose reduced matrix has fewer columns than contributors)."""
-    if first_route == "single" or n_multi > 1 or n_rows > max_rows:
+    its own, every sample of a multi-run (the fold of the runs' posteriors, em.py:156, is theirs) unless runs="batch"
+    and there are at most FINISH_RUNS_MAX runs, one of more than max_rows rows, and -- once its contributors are known --
+    one with more than FINISH_KMAX of them (or with a haplogroup named twice, whose reduced matrix has fewer columns than
+    contributors)."""
+    if runs not in ("single", "batch"):
+        raise ValueError("finish_many: runs must be 'single' or 'batch', not %r" % (runs,))
+    if first_route == "single" or n_rows > max_rows or (n_multi > 1 and (runs == "single" or n_multi > FINISH_RUNS_MAX)):
         return "single"
     if n_contribs is not None and (n_contribs > FINISH_KMAX or (n_columns is not None and n_columns != n_contribs)):
         return "single"
@@ -777,7 +783,7 @@ def _finish_batch(samples, wts_d, ids):
 
 
 def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refine_inits=None, max_rows=None,
-                want_posterior=False, var_tables=None):
+                want_posterior=False, var_tables=None, runs="single"):
     """
     What mixemt reports for a sample after its EM (bin/mixemt:298-323: get_contributors, the refinement run_em on the
     contributors' columns with update_contribs, assign_read_indexes) for ALL samples of one em.run_em_many call in
@@ -802,7 +808,18 @@ def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refin
         draw of sample s + 1 follows the refinement draw of sample s); or a list with [K_s] proportions per sample (None
         where nothing is refined), in the REDUCED matrix's column order: ascending haplogroup index (preprocess.py:247-251),
         not contributor order.
+        With args.n_multi = B > 1: [B][K_s] per sample; None draws B vectors per refined sample, still sample after sample
+        (sample s's B draws, then sample s + 1's), whichever route a sample takes.
     max_rows: a sample of more rows takes the per-sample route (default FINISH_MAX_ROWS).
+    runs: what happens to the samples when args.n_multi > 1 (mixemt's -M).  "single", the default: every sample takes the
+        per-sample route.  "batch": a sample stays on the batch route whenever everything else allows it -- its first EM
+        was batched, at most max_rows rows, at most 16 contributors, no haplogroup named twice -- and args.n_multi <= 64;
+        the vote and the read assignment then work on the runs' posteriors folded in run order as run_em folds them
+        (mxm_votes_samples_runs, mxm_assign_reads_samples_runs) and the refinement runs one workgroup per (sample, run)
+        (mxm_em_loop_samples_narrow_runs).  `refined` then holds props = the runs' geometric mean (em._fold_runs), iters /
+        done / l1 as lists of B, inits / ln_theta_k / ln_theta_next as [B][K_s]; `posterior` is the folded reduced
+        posterior; unrefined, the rows are assigned from the first EM's folded posterior and folded props.  Anything else
+        is a ValueError.  With args.n_multi == 1 the keyword changes nothing.
     Returns one dict per sample:
         contribs    [[hapNN, haplogroup, proportion], ...] as get_contributors and update_contribs leave it
         vote_order, votes   what vote_table_from_records returns (haplogroups in first-seen order, unweighted votes [H])
@@ -812,8 +829,8 @@ def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refin
                     the first EM's posterior, contributors' columns only) or nothing contributes
         assigned    an AssignedReads (contributor order); row_label: its int32 [R_s] ordinals, -1 = unassigned
         route       "batch", or "single": the sample went through the per-sample functions -- its first EM ran on its
-                    own, args.n_multi > 1 (the fold of several runs' posteriors, em.py:156, stays with the per-sample
-                    path), more than max_rows rows, or more than 16 contributors
+                    own, args.n_multi > 1 without runs="batch" (or more than 64 runs), more than max_rows rows, or more
+                    than 16 contributors
         var_check   "device" or "host": where the sample's candidates were checked; None when the check is off
                     (args.var_check false, or args.contributors given)
         posterior   always present; None unless want_posterior is set (an addition to mixemt's own outputs, for tests and
@@ -825,12 +842,14 @@ def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refin
     hap_index, fixed = _finish_check(samples, results, haplogroups, args, obs, phylo, var_tables)
     n = len(samples)
     n_multi = int(getattr(args, "n_multi", 1))
+    if runs not in ("single", "batch"):
+        raise ValueError("finish_many: runs must be 'single' or 'batch', not %r" % (runs,))
     max_rows = FINISH_MAX_ROWS if max_rows is None else int(max_rows)
     dev = require_gpu()
     wts_d = [as_device(w, torch.float64, dev).reshape(-1) for _, w in samples]
     if any(int(w.numel()) != m.n_rows for w, (m, _) in zip(wts_d, samples)):
         raise ValueError("finish_many: weights do not match the samples' rows")
-    route = [_finish_route(samples[s][0].n_rows, results[s].get("route"), n_multi, max_rows) for s in range(n)]
+    route = [_finish_route(samples[s][0].n_rows, results[s].get("route"), n_multi, max_rows, runs=runs) for s in range(n)]
     contribs, orders, counts = [None] * n, [None] * n, [None] * n
     checked = bool(args.var_check) and fixed is None
     cohort = checked and _is_cohort_pileup(obs)
@@ -851,8 +870,14 @@ def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refin
     first_batch = lse_all = None
     if voted:
         first_batch = _finish_batch(samples, wts_d, voted)
-        ln_props = numpy.stack([numpy.atleast_2d(results[s]["ln_theta_k"])[0] for s in voted])
-        _, votes_w, counts_h, first_h, lse_all, errors = first_batch.votes(ln_props, want_lse=not args.refine_ests)
+        if n_multi > 1:                                      # (runs="batch": the vote over the runs' folded posterior)
+            ln_props = numpy.stack([numpy.atleast_2d(results[s]["ln_theta_k"]) for s in voted])
+            if ln_props.shape[1] != n_multi:
+                raise ValueError("finish_many: args.n_multi = %d, the results hold %d runs" % (n_multi, ln_props.shape[1]))
+            _, votes_w, counts_h, first_h, lse_all, errors = first_batch.votes_runs(ln_props, want_lse=not args.refine_ests)
+        else:
+            ln_props = numpy.stack([numpy.atleast_2d(results[s]["ln_theta_k"])[0] for s in voted])
+            _, votes_w, counts_h, first_h, lse_all, errors = first_batch.votes(ln_props, want_lse=not args.refine_ests)
         for j, s in enumerate(voted):
             if errors[j]:
                 raise ValueError("finish_many: sample %d has a row without a record (ndist outside 1 .. 1024)" % s)
@@ -894,7 +919,7 @@ def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refin
             plans[s] = _finish_columns(contribs[s], hap_index)
             if route[s] == "batch":
                 route[s] = _finish_route(samples[s][0].n_rows, results[s].get("route"), n_multi, max_rows,
-                                         len(contribs[s]), len(set(plans[s][0])))
+                                         len(contribs[s]), len(set(plans[s][0])), runs=runs)
     refine = bool(args.refine_ests)
     inits = _finish_inits([len(set(plans[s][0])) if (refine and plans[s] is not None) else None for s in range(n)],
                           refine_inits, args.init_alpha, n_multi)
@@ -917,11 +942,24 @@ def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refin
     batch = first_batch if ids == voted else _finish_batch(samples, wts_d, ids)
     ld, cols, ncol, perm = _finish_tables([plans[s] for s in ids])
     mat = batch.gather(cols, ncol, ld)
-    ln_theta = numpy.full((len(ids), ld), -numpy.inf)
+    many = n_multi > 1
+    ln_theta = numpy.full((len(ids), n_multi, ld) if many else (len(ids), ld), -numpy.inf)
     log_props = numpy.full((len(ids), ld), -numpy.inf)
     refined = [None] * len(ids)
     lse = None
-    if refine:
+    if refine and many:
+        ln_cur, ln_new, states = batch.em_loop_runs(mat, ld, ncol, [inits[s] for s in ids], args.tolerance, args.max_iter)
+        for j, s in enumerate(ids):
+            k = int(ncol[j])
+            props = em._fold_runs(ln_new[j, :, :k])                             # em.py:155, :163
+            refined[j] = {"props": props, "iters": [st[1] for st in states[j]], "done": [st[0] for st in states[j]],
+                          "l1": [st[2] for st in states[j]], "inits": inits[s], "ln_theta_k": ln_cur[j, :, :k].copy(),
+                          "ln_theta_next": ln_new[j, :, :k].copy()}
+            contribs[s] = update_contribs(contribs[s], (props, None), plans[s][2])
+            ln_theta[j, :, :k] = ln_cur[j, :, :k]
+            with numpy.errstate(divide="ignore"):
+                log_props[j, :k] = numpy.log(props)
+    elif refine:
         ln_cur, ln_new, states = batch.em_loop(mat, ld, ncol, [inits[s][0] for s in ids], args.tolerance, args.max_iter)
         for j, s in enumerate(ids):
             k = int(ncol[j])
@@ -942,11 +980,14 @@ def finish_many(samples, results, haplogroups, args, phylo=None, obs=None, refin
             lse = torch.cat([lse_all[int(start[at[s]]):int(start[at[s] + 1])] for s in ids])
         for j, s in enumerate(ids):
             k = int(ncol[j])
-            ln_theta[j, :k] = numpy.atleast_2d(results[s]["ln_theta_k"])[0][cols[j, :k]]
+            if many:
+                ln_theta[j, :, :k] = numpy.atleast_2d(results[s]["ln_theta_k"])[:, cols[j, :k]]
+            else:
+                ln_theta[j, :k] = numpy.atleast_2d(results[s]["ln_theta_k"])[0][cols[j, :k]]
             with numpy.errstate(divide="ignore"):
                 log_props[j, :k] = numpy.log(numpy.asarray(results[s]["props"], dtype=numpy.float64)[cols[j, :k]])
-    assigned, post = batch.assign(mat, ld, ncol, perm, ln_theta, log_props, lse, args.min_fold,
-                                  want_post=want_posterior and refine)
+    assigned, post = (batch.assign_runs if many else batch.assign)(mat, ld, ncol, perm, ln_theta, log_props, lse, args.min_fold,
+                                                                   want_post=want_posterior and refine)
     labels = assigned.cpu().numpy()
     for j, s in enumerate(ids):
         lo, hi = int(batch.row0[j]), int(batch.row0[j + 1])

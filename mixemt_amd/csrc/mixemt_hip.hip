@@ -29,6 +29,7 @@
 //   fused_coded_kernels.hpp  em_fused_coded_kernel (the whole EM loop over records in one persistent launch)
 //   fused_narrow_kernels.hpp  em_fused_narrow_kernel (the same for the refinement EM's few columns: the matrix in registers)
 //   samples_finish_kernels.hpp  votes, column gather, refinement EM loop and read assignment of many samples per launch
+//   samples_runs_kernels.hpp    their forms for samples of several EM runs (the fold of the runs' posteriors)
 //   samples_kernels.hpp em_iter_samples_kernel, samples_colreduce_kernel (the EM iteration of many samples in one launch: a tile of
 //                       one sample's rows per workgroup)
 //   aln_encode.hpp      HOST code: mxm_aln_encode, the batched alignment front end (process_reads + reduce_reads + row order)
@@ -78,6 +79,7 @@
 #include "fused_narrow_kernels.hpp"
 #include "samples_kernels.hpp"
 #include "samples_finish_kernels.hpp"
+#include "samples_runs_kernels.hpp"
 #include "exchange.hpp"
 #include "aln_walk.hpp"
 #include "observe_kernels.hpp"
@@ -2377,6 +2379,156 @@ extern "C" int mxm_assign_reads_samples(const mxm_coded *c, const int64_t *row0_
         }
     });
     if (!launched) return fail(-1, "mxm_assign_reads_samples: ld = %d has no kernel instance", ld);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- the same for samples of B EM runs each (samples_runs_kernels.hpp; include/mixemt_hip_samples_runs.h) ----
+// The workspace is the one-run layout: the tile table and the per-sample tables have no run dimension (the per-run
+// tables are the caller's device arrays); B only has to be one the entries take.
+static bool runs_ok(int32_t B) { return B >= 2 && B <= MXM_SAMPLES_RUNS_MAX; }
+static int runs_check(const char *who, int32_t B) {
+    if (!runs_ok(B)) return fail(-1, "%s: B = %d runs per sample: 2 .. %d are taken (one run: the entries of mixemt_hip_samples_finish.h)",
+                                 who, B, MXM_SAMPLES_RUNS_MAX);
+    return 0;
+}
+extern "C" size_t mxm_samples_runs_workspace_bytes(int64_t n_tiles, int32_t S, int32_t B, int32_t ld) {
+    if (!runs_ok(B)) return 0;
+    return mxm_samples_finish_workspace_bytes(n_tiles, S, ld);
+}
+static int runs_ws_check(const char *who, const void *ws, size_t ws_bytes, int64_t n_tiles, int32_t S, int32_t B, int32_t ld) {
+    if (ws == nullptr || ws_bytes < mxm_samples_runs_workspace_bytes(n_tiles, S, B, ld) || (reinterpret_cast<uintptr_t>(ws) & 15))
+        return fail(-1, "%s: workspace too small (or not 16-byte aligned)", who);
+    return 0;
+}
+
+extern "C" int mxm_votes_samples_runs(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, int32_t B, const double *w,
+                                      const double *ln_props, const double *props, const double *rowmax, int32_t *best,
+                                      double *votes, int64_t *counts, int64_t *first, double *lse, mxm_em_state *state, void *ws,
+                                      size_t ws_bytes, void *stream) {
+    MXM_ENTER();
+    int64_t n_tiles = 0;
+    RC_TRY(samples_check(c, row0_host, S, H, "mxm_votes_samples_runs", &n_tiles));
+    RC_TRY(runs_check("mxm_votes_samples_runs", B));
+    if (ln_props == nullptr || props == nullptr || rowmax == nullptr || best == nullptr || votes == nullptr || first == nullptr)
+        return fail(-1, "mxm_votes_samples_runs: bad arguments (ln_props, props, rowmax, best, votes and first are required)");
+    RC_TRY(runs_ws_check("mxm_votes_samples_runs", ws, ws_bytes, n_tiles, S, B, 0));
+    hipStream_t s = (hipStream_t)stream;
+    const finish_ws L = finish_layout(ws, n_tiles, (int)S, 0);
+    const size_t vlds = (size_t)H * (sizeof(double) + 2 * sizeof(int));
+    RC_TRY(dynamic_lds_ok(reinterpret_cast<const void *>(&votes_sum_samples_kernel), vlds, "votes_sum_samples_kernel",
+                          "mxm_votes_samples_runs", H, "too wide for the vote kernel"));
+    RC_TRY(finish_upload(row0_host, (int)S, n_tiles, 0, nullptr, nullptr, nullptr, L, s));
+    hipLaunchKernelGGL(votes_best_samples_runs_kernel, dim3((unsigned)n_tiles), dim3(SFIN_THREADS), 0, s, c->rec, c->rec_off, c->ndist,
+                       coded_ld(H), (int)H, (int)B, (const mxm_sample_tile *)L.tiles, ln_props, props, rowmax, best, lse);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(votes_sum_samples_kernel, dim3((unsigned)S), dim3(SFIN_THREADS), vlds, s, (const int32_t *)best, w,
+                       (const int64_t *)L.row0, (int)H, votes, counts, first, state);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int mxm_em_loop_samples_narrow_runs(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, int32_t B,
+                                               const double *M, int32_t ld, const int32_t *ncol_host, const double *w,
+                                               double *props_cur, double *ln_cur, double *ln_new, mxm_em_state *state, double tol,
+                                               int32_t max_iter, int32_t check_every, double *E, void *ws, size_t ws_bytes,
+                                               void *stream, mxm_em_state *state_host) {
+    MXM_ENTER();
+    int64_t n_tiles = 0;
+    RC_TRY(samples_check(c, row0_host, S, H, "mxm_em_loop_samples_narrow_runs", &n_tiles));
+    RC_TRY(runs_check("mxm_em_loop_samples_narrow_runs", B));
+    if (M == nullptr || props_cur == nullptr || ln_cur == nullptr || ln_new == nullptr || state == nullptr || state_host == nullptr)
+        return fail(-1, "mxm_em_loop_samples_narrow_runs: bad arguments");
+    RC_TRY(finish_cols_check("mxm_em_loop_samples_narrow_runs", S, H, ld, ncol_host, nullptr, nullptr));
+    RC_TRY(runs_ws_check("mxm_em_loop_samples_narrow_runs", ws, ws_bytes, n_tiles, S, B, ld));
+    // the linearised samples: in each workgroup's LDS where they fit, else in the global copy E, formed once below
+    int64_t lds_doubles = 0;
+    bool spills = false;
+    for (int32_t b = 0; b < S; ++b) {
+        const int64_t cells = (row0_host[b + 1] - row0_host[b]) * (int64_t)ncol_host[b];
+        if (cells <= SFIN_LDS_DOUBLES) lds_doubles = std::max(lds_doubles, cells);
+        else spills = true;
+    }
+    if (spills && E == nullptr)
+        return fail(-1, "mxm_em_loop_samples_narrow_runs: a sample of more than %d cells needs the global copy E", SFIN_LDS_DOUBLES);
+    if (check_every < 1) check_every = 1;
+    if (T.progress != nullptr && check_every > T.progress_every) check_every = T.progress_every;
+    hipStream_t s = (hipStream_t)stream;
+    const finish_ws L = finish_layout(ws, n_tiles, (int)S, (int)ld);
+    const size_t lds = (size_t)lds_doubles * sizeof(double);
+    const int n_entries = (int)S * (int)B;
+    int lds_rc = -1;
+    (void)dispatch_width<SFIN_KMAX>((int)ld, [&](auto n) {
+        constexpr int LD = decltype(n)::value;
+        if constexpr (LD == 4 || LD == 8 || LD == 16)
+            lds_rc = dynamic_lds_ok(reinterpret_cast<const void *>(&em_loop_samples_narrow_runs_kernel<LD>), lds,
+                                    "em_loop_samples_narrow_runs_kernel");
+    });
+    RC_TRY(lds_rc);
+    auto launch = [&](int chunk, bool linearise) -> int {
+        bool launched = false;
+        (void)dispatch_width<SFIN_KMAX>((int)ld, [&](auto n) {
+            constexpr int LD = decltype(n)::value;
+            if constexpr (LD == 4 || LD == 8 || LD == 16) {
+                if (linearise)
+                    hipLaunchKernelGGL((linearise_samples_runs_kernel<LD>), dim3((unsigned)n_tiles), dim3(64), 0, s, M,
+                                       (const mxm_sample_tile *)L.tiles, (const int64_t *)L.row0, (const int32_t *)L.ncol,
+                                       (int)SFIN_LDS_DOUBLES, E);
+                else
+                    hipLaunchKernelGGL((em_loop_samples_narrow_runs_kernel<LD>), dim3((unsigned)n_entries), dim3(SFIN_THREADS), lds, s,
+                                       M, E, w, (const int64_t *)L.row0, (const int32_t *)L.ncol, (int)B, ln_cur, ln_new, props_cur,
+                                       state, tol, (int)max_iter, chunk, (int)lds_doubles);
+                launched = true;
+            }
+        });
+        if (!launched) return fail(-1, "mxm_em_loop_samples_narrow_runs: ld = %d has no kernel instance", ld);
+        HIP_TRY(hipGetLastError());
+        return 0;
+    };
+    RC_TRY(finish_upload(row0_host, (int)S, n_tiles, (int)ld, ncol_host, nullptr, nullptr, L, s));
+    RC_TRY(read_state(state_host, state, n_entries, s));
+    auto running = [&]() {
+        int n = 0;
+        for (int e = 0; e < n_entries; ++e) n += (state_host[e].done == 0 && ncol_host[e / B] > 0) ? 1 : 0;
+        return n;
+    };
+    if (spills && max_iter > 0 && running() > 0) RC_TRY(launch(0, true));
+    while (max_iter > 0 && running() > 0) {
+        RC_TRY(launch((int)check_every, false));
+        RC_TRY(read_state(state_host, state, n_entries, s));
+        if (T.progress != nullptr) T.progress(state_host, n_entries, T.progress_user);
+    }
+    return 0;
+}
+
+extern "C" int mxm_assign_reads_samples_runs(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, int32_t B,
+                                             const double *M, int32_t ld, const int32_t *ncol_host, const int32_t *perm_host,
+                                             const double *ln_theta, const double *props, const double *log_props,
+                                             const double *lse, double log_min_fold, int32_t *assigned, double *post, void *ws,
+                                             size_t ws_bytes, void *stream) {
+    MXM_ENTER();
+    int64_t n_tiles = 0;
+    RC_TRY(samples_check(c, row0_host, S, H, "mxm_assign_reads_samples_runs", &n_tiles));
+    RC_TRY(runs_check("mxm_assign_reads_samples_runs", B));
+    if (M == nullptr || perm_host == nullptr || ln_theta == nullptr || props == nullptr || log_props == nullptr || assigned == nullptr)
+        return fail(-1, "mxm_assign_reads_samples_runs: bad arguments");
+    RC_TRY(finish_cols_check("mxm_assign_reads_samples_runs", S, H, ld, ncol_host, nullptr, perm_host));
+    RC_TRY(runs_ws_check("mxm_assign_reads_samples_runs", ws, ws_bytes, n_tiles, S, B, ld));
+    hipStream_t s = (hipStream_t)stream;
+    const finish_ws L = finish_layout(ws, n_tiles, (int)S, (int)ld);
+    RC_TRY(finish_upload(row0_host, (int)S, n_tiles, (int)ld, ncol_host, nullptr, perm_host, L, s));
+    const double neg_log_runs = -log((double)B);            // the host's logarithm, as em.collect_result hands it to mxm_add_scalar
+    bool launched = false;
+    (void)dispatch_width<SFIN_KMAX>((int)ld, [&](auto n) {
+        constexpr int LD = decltype(n)::value;
+        if constexpr (LD == 4 || LD == 8 || LD == 16) {
+            hipLaunchKernelGGL((assign_samples_runs_kernel<LD>), dim3((unsigned)n_tiles), dim3(64), 0, s, M,
+                               (const mxm_sample_tile *)L.tiles, (const int32_t *)L.ncol, (const int32_t *)L.perm, (int)B, ln_theta,
+                               props, log_props, lse, neg_log_runs, log_min_fold, assigned, post);
+            launched = true;
+        }
+    });
+    if (!launched) return fail(-1, "mxm_assign_reads_samples_runs: ld = %d has no kernel instance", ld);
     HIP_TRY(hipGetLastError());
     return 0;
 }

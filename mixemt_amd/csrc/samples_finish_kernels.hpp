@@ -164,6 +164,22 @@ __global__ __launch_bounds__(SFIN_THREADS) void gather_samples_kernel(
     }
 }
 
+// e[k] = exp(x[k] - rowmax) of one reduced row x [LD] with K columns: 0 in the pad columns, no shift for a row without a
+// finite maximum
+template <int LD>
+__device__ __forceinline__ void sfin_linear_row(const double *__restrict__ row, int K, double (&e)[LD]) {
+    double x[LD];
+    double m = -INFINITY;
+#pragma unroll
+    for (int k = 0; k < LD; ++k) {
+        x[k] = (k < K) ? row[k] : -INFINITY;
+        m = fmax(m, x[k]);
+    }
+    const double shift = isfinite(m) ? m : 0.0;
+#pragma unroll
+    for (int k = 0; k < LD; ++k) e[k] = exp(x[k] - shift);  // exp(-inf) = 0
+}
+
 // ------------------------------------------------------------------------------------------
 // The refinement EM of one sample per workgroup (em.py:126-143 on R_s x K_s, K_s <= LD): em_fused_narrow_kernel's
 // arithmetic and its stop / resume contract, without its grid -- the sample's rows are dealt over the workgroup's
@@ -174,43 +190,30 @@ __global__ __launch_bounds__(SFIN_THREADS) void gather_samples_kernel(
 // lds_doubles, else into the global copy E [R][LD], which the iterations then re-read.  A launch runs at most `chunk`
 // iterations; the host re-launches until every state is done.
 // ------------------------------------------------------------------------------------------
-template <int LD>
-__global__ __launch_bounds__(SFIN_THREADS, 2) void em_loop_samples_narrow_kernel(
-    const double *__restrict__ M, double *__restrict__ E, const double *__restrict__ w, const int64_t *__restrict__ row0,
-    const int32_t *__restrict__ ncol, double *__restrict__ ln_cur, double *__restrict__ ln_new, double *__restrict__ props_cur,
-    mxm_em_state *__restrict__ state, double tol, int max_iter, int chunk, int lds_doubles) {
+// The loop of ONE workgroup on n rows x K columns: Ms / Es / ws point at the sample's first row, ln_cur / ln_new /
+// props_cur [LD] and st at the entry's own tables.  E_READY: a pass before the launch has formed the sample's e in Es
+// (samples_runs_kernels.hpp: several workgroups share one sample there), so this workgroup only reads it.
+template <int LD, bool E_READY>
+__device__ __forceinline__ void sfin_em_loop_body(const double *__restrict__ Ms, double *__restrict__ Es, const double *__restrict__ ws,
+                                                  int64_t n, int K, double *__restrict__ ln_cur, double *__restrict__ ln_new,
+                                                  double *__restrict__ props_cur, mxm_em_state *__restrict__ st, double tol,
+                                                  int max_iter, int chunk, int lds_doubles) {
     constexpr int THREADS = SFIN_THREADS, NW = THREADS / 64;
     extern __shared__ double sfin_e[];
     __shared__ double s_red[LD][NW];
-    const int s = blockIdx.x;
-    mxm_em_state *st = state + s;
-    if (st->done != 0) return;                             // written before the launch
-    const int K = ncol[s];
-    if (K < 1 || K > LD) return;
     const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
-    const int64_t lo = row0[s], n = row0[s + 1] - lo;
     const bool in_lds = n * K <= (int64_t)lds_doubles;     // uniform
-    const double *Ms = M + lo * LD;
-    double *Es = E + lo * LD;
-    const double *ws = (w != nullptr) ? w + lo : nullptr;
 
     // ---- linearise once: e = exp(M - rowmax), pad columns 0 ----
-    for (int64_t r = t; r < n; r += THREADS) {
-        double x[LD];
-        double m = -INFINITY;
+    for (int64_t r = t; r < n && (in_lds || !E_READY); r += THREADS) {
+        double e[LD];
+        sfin_linear_row<LD>(Ms + r * LD, K, e);
 #pragma unroll
         for (int k = 0; k < LD; ++k) {
-            x[k] = (k < K) ? Ms[r * LD + k] : -INFINITY;
-            m = fmax(m, x[k]);
-        }
-        const double shift = isfinite(m) ? m : 0.0;
-#pragma unroll
-        for (int k = 0; k < LD; ++k) {
-            const double e = exp(x[k] - shift);             // exp(-inf) = 0
             if (in_lds) {
-                if (k < K) sfin_e[k * n + r] = e;
+                if (k < K) sfin_e[k * n + r] = e[k];
             } else {
-                Es[r * LD + k] = e;
+                Es[r * LD + k] = e[k];
             }
         }
     }
@@ -221,8 +224,8 @@ __global__ __launch_bounds__(SFIN_THREADS, 2) void em_loop_samples_narrow_kernel
     double lc[LD], p[LD], ln_next[LD];
 #pragma unroll
     for (int k = 0; k < LD; ++k) {
-        lc[k] = (k < K) ? ln_cur[(int64_t)s * LD + k] : -INFINITY;
-        p[k] = (k < K) ? (iters > 0 ? props_cur[(int64_t)s * LD + k] : exp(lc[k])) : 0.0;
+        lc[k] = (k < K) ? ln_cur[k] : -INFINITY;
+        p[k] = (k < K) ? (iters > 0 ? props_cur[k] : exp(lc[k])) : 0.0;
         ln_next[k] = lc[k];
     }
     for (int it = 0; it < chunk && done == 0; ++it) {
@@ -287,9 +290,9 @@ __global__ __launch_bounds__(SFIN_THREADS, 2) void em_loop_samples_narrow_kernel
 #pragma unroll
     for (int k = 0; k < LD; ++k) {
         if (t == k && k < K) {
-            ln_cur[(int64_t)s * LD + k] = lc[k];
-            props_cur[(int64_t)s * LD + k] = p[k];
-            if (done > 0) ln_new[(int64_t)s * LD + k] = ln_next[k];
+            ln_cur[k] = lc[k];
+            props_cur[k] = p[k];
+            if (done > 0) ln_new[k] = ln_next[k];
         }
     }
     if (t == 0) {
@@ -297,6 +300,21 @@ __global__ __launch_bounds__(SFIN_THREADS, 2) void em_loop_samples_narrow_kernel
         st->l1 = l1;
         st->done = done;
     }
+}
+
+template <int LD>
+__global__ __launch_bounds__(SFIN_THREADS, 2) void em_loop_samples_narrow_kernel(
+    const double *__restrict__ M, double *__restrict__ E, const double *__restrict__ w, const int64_t *__restrict__ row0,
+    const int32_t *__restrict__ ncol, double *__restrict__ ln_cur, double *__restrict__ ln_new, double *__restrict__ props_cur,
+    mxm_em_state *__restrict__ state, double tol, int max_iter, int chunk, int lds_doubles) {
+    const int s = blockIdx.x;
+    mxm_em_state *st = state + s;
+    if (st->done != 0) return;                             // written before the launch
+    const int K = ncol[s];
+    if (K < 1 || K > LD) return;
+    const int64_t lo = row0[s], n = row0[s + 1] - lo;
+    sfin_em_loop_body<LD, false>(M + lo * LD, E + lo * LD, (w != nullptr) ? w + lo : nullptr, n, K, ln_cur + (int64_t)s * LD,
+                                 ln_new + (int64_t)s * LD, props_cur + (int64_t)s * LD, st, tol, max_iter, chunk, lds_doubles);
 }
 
 // ------------------------------------------------------------------------------------------

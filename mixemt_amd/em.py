@@ -832,8 +832,12 @@ class SampleFinish(object):
     (mxm_gather_columns_samples), the refinement loop with ONE workgroup per sample (mxm_em_loop_samples_narrow) and the
     read assignment (mxm_assign_reads_samples).  rowmax [R]: the records' row maxima (CodedMatrix.rowmax), for the row
     normaliser of the unrefined assignment.  Every per-sample table is [S][ld] with ld = 4, 8 or 16.
+    votes_runs / em_loop_runs / assign_runs are the same stages for samples of B EM runs each (mxm_votes_samples_runs,
+    mxm_em_loop_samples_narrow_runs, mxm_assign_reads_samples_runs): per-run tables [S][B][...], the vote and the assignment
+    over the runs' posteriors folded in run order (em.py:145-161), one workgroup per (sample, run) in the loop.
     """
     KMAX = 16
+    LDS_CELLS = 9216                # cells (R_s x ncol) up to which the refinement loops linearise a sample in LDS
 
     def __init__(self, rec, rec_off, ndist, wts, rowmax, row0, n_haps):
         self.lib = _lib.load()
@@ -932,6 +936,101 @@ class SampleFinish(object):
                                                      ptr(lse), float(numpy.log(min_fold)), assigned.data_ptr(), ptr(post),
                                                      self.ws.data_ptr(), self.ws_bytes, current_stream()),
                    "mxm_assign_reads_samples")
+        return assigned, post
+
+    # ---- samples of several EM runs each (include/mixemt_hip_samples_runs.h): every per-run table is [S][B][...] ----
+    def _runs_ws(self, n_runs, ld):
+        """The workspace for B runs per sample (mxm_samples_runs_workspace_bytes): the object's own, grown if need be."""
+        need = int(self.lib.mxm_samples_runs_workspace_bytes(self.n_tiles, self.n_entries, n_runs, ld))
+        if need == 0:
+            raise ValueError("the batched second half takes 2 .. 64 runs per sample, not %d" % n_runs)
+        if need > self.ws_bytes:
+            self.ws_bytes = need
+            self.ws = torch.empty(need // 8 + 2, dtype=torch.float64, device=self.dev)
+        return need
+
+    def votes_runs(self, ln_props, want_lse=False):
+        """votes() over the FOLDED posterior of B runs per sample (em.py:145-161): ln_props [S][B][H] (host).  Returns
+        (best int32[R] device, votes [S][H], counts [S][H], first [S][H] on the host, lse [R][B] device or None, error
+        flags [S])."""
+        n, n_haps = self.n_entries, self.n_haps
+        host = numpy.ascontiguousarray(ln_props, dtype=numpy.float64)
+        if host.ndim != 3 or host.shape[0] != n or host.shape[2] != n_haps:
+            raise ValueError("ln_props must be [%d][B][%d]" % (n, n_haps))
+        n_runs = host.shape[1]
+        if self.rowmax is None:
+            raise ValueError("the row normaliser needs the records' rowmax")
+        ws_bytes = self._runs_ws(n_runs, 0)
+        lnp = torch.from_numpy(host).to(self.dev)
+        props = torch.from_numpy(numpy.exp(host)).to(self.dev)
+        best = torch.empty(self.n_rows, dtype=torch.int32, device=self.dev)
+        votes = torch.empty((n, n_haps), dtype=torch.float64, device=self.dev)
+        table = torch.empty((2, n, n_haps), dtype=torch.int64, device=self.dev)      # counts, first-seen rows
+        lse = torch.empty((self.n_rows, n_runs), dtype=torch.float64, device=self.dev) if want_lse else None
+        state = new_state(n, self.dev)
+        _lib.check(self.lib.mxm_votes_samples_runs(ctypes.byref(self.coded), self.row0_ptr, n, n_haps, n_runs,
+                                                   self.wts.data_ptr(), lnp.data_ptr(), props.data_ptr(), self.rowmax.data_ptr(),
+                                                   best.data_ptr(), votes.data_ptr(), table[0].data_ptr(), table[1].data_ptr(),
+                                                   ptr(lse), state.data_ptr(), self.ws.data_ptr(), ws_bytes, current_stream()),
+                   "mxm_votes_samples_runs")
+        raw = state.cpu().numpy().tobytes()
+        errors = [st.error != 0 for st in (_lib.EmState * n).from_buffer_copy(raw)]
+        table_h = table.cpu().numpy()
+        return best, votes.cpu().numpy(), table_h[0], table_h[1], lse, errors
+
+    def em_loop_runs(self, mat, ld, ncol, inits, tolerance, max_iter, check_every=16):
+        """em_loop with B runs per sample, one workgroup per (sample, run): inits[s] = [B][ncol[s]] linear.  Returns
+        (ln_cur, ln_new) as [S][B][ld] numpy arrays and [(done, iters, l1)] per sample, one list of B each."""
+        n = self.n_entries
+        ncol_h, ncol_p = self._i32(ncol)
+        n_runs = numpy.atleast_2d(numpy.asarray(inits[0])).shape[0]
+        p0 = numpy.zeros((n, n_runs, ld), dtype=numpy.float64)
+        for s in range(n):
+            p0[s, :, :ncol_h[s]] = numpy.asarray(inits[s], dtype=numpy.float64).reshape(n_runs, ncol_h[s])
+        ln0, p0 = log_inits(p0.reshape(n * n_runs, ld))
+        ws_bytes = self._runs_ws(n_runs, ld)
+        props_cur = torch.from_numpy(p0).to(self.dev)
+        ln_cur = torch.from_numpy(ln0).to(self.dev)
+        ln_new = ln_cur.clone()
+        state = new_state(n * n_runs, self.dev)
+        host_state = (_lib.EmState * (n * n_runs))()
+        spills = any(int(self.row0[s + 1] - self.row0[s]) * int(ncol_h[s]) > self.LDS_CELLS for s in range(n))
+        lin = device_empty((self.n_rows, ld), torch.float64, self.dev, "the linearised reduced matrices") if spills else None
+        _lib.check(self.lib.mxm_em_loop_samples_narrow_runs(ctypes.byref(self.coded), self.row0_ptr, n, self.n_haps, n_runs,
+                                                            mat.data_ptr(), ld, ncol_p, self.wts.data_ptr(), props_cur.data_ptr(),
+                                                            ln_cur.data_ptr(), ln_new.data_ptr(), state.data_ptr(),
+                                                            float(tolerance), int(max_iter), int(check_every), ptr(lin),
+                                                            self.ws.data_ptr(), ws_bytes, current_stream(), host_state),
+                   "mxm_em_loop_samples_narrow_runs")
+        states = [(st.done, st.iters, st.l1) for st in host_state]
+        return (ln_cur.cpu().numpy().reshape(n, n_runs, ld), ln_new.cpu().numpy().reshape(n, n_runs, ld),
+                [states[s * n_runs:(s + 1) * n_runs] for s in range(n)])
+
+    def assign_runs(self, mat, ld, ncol, perm, ln_theta, log_props, lse, min_fold, want_post=False):
+        """assign() under the folded reduced posterior of B runs: ln_theta [S][B][ld] (log theta_k per run), log_props
+        [S][ld] (the log of the FOLDED proportions), lse [R][B] device or None."""
+        n = self.n_entries
+        ncol_h, ncol_p = self._i32(ncol)
+        perm_h, perm_p = self._i32(perm)
+        ln_h = numpy.ascontiguousarray(ln_theta, dtype=numpy.float64)
+        if ln_h.ndim != 3 or ln_h.shape[0] != n or ln_h.shape[2] != ld:
+            raise ValueError("ln_theta must be [%d][B][%d]" % (n, ld))
+        n_runs = ln_h.shape[1]
+        if lse is not None and tuple(lse.shape) != (self.n_rows, n_runs):
+            raise ValueError("lse must be [%d][%d]" % (self.n_rows, n_runs))
+        ws_bytes = self._runs_ws(n_runs, ld)
+        lse_d = None if lse is None else lse.contiguous()
+        ln_d = torch.from_numpy(ln_h).to(self.dev)
+        props_d = torch.from_numpy(numpy.exp(ln_h)).to(self.dev)
+        lp_d = torch.from_numpy(numpy.ascontiguousarray(log_props, dtype=numpy.float64)).to(self.dev)
+        assigned = torch.empty(self.n_rows, dtype=torch.int32, device=self.dev)
+        post = device_empty((self.n_rows, ld), torch.float64, self.dev, "the reduced posteriors") if want_post else None
+        _lib.check(self.lib.mxm_assign_reads_samples_runs(ctypes.byref(self.coded), self.row0_ptr, n, self.n_haps, n_runs,
+                                                          mat.data_ptr(), ld, ncol_p, perm_p, ln_d.data_ptr(), props_d.data_ptr(),
+                                                          lp_d.data_ptr(), ptr(lse_d),
+                                                          float(numpy.log(min_fold)), assigned.data_ptr(), ptr(post),
+                                                          self.ws.data_ptr(), ws_bytes, current_stream()),
+                   "mxm_assign_reads_samples_runs")
         return assigned, post
 
 

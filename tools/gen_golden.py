@@ -51,6 +51,9 @@ Fixtures (SURVEY.md section 8 c):
         dict, the final key and the round of every alignment, the consensus strings, the verbose text and the files;
         plus a case where nothing is assigned (no contributor keys) and one whose cons_cov calls nothing.
         --cache DIR keeps the reference's matrix and EM result of g18 between runs of the generator.
+    g19 the REFINED multi-run (-M 3): g13's contributor table (read from g13's file in --out) -> reduce_em_matrix -> run_em
+        with n_multi = 3 on 600 x 3 -> update_contribs -> assign_read_indexes: the runs' inits, stops and folded
+        proportions, the folded reduced posterior and every row's label
 """
 
 import argparse
@@ -772,6 +775,43 @@ def main():
              contrib_names=numpy.array("\n".join(names)), contrib_haps=numpy.array("\n".join(c[1] for c in contribs)),
              contrib_props=numpy.array([c[2] for c in contribs]), assigned=assigned, vote_text=numpy.array(vote_text),
              props=props, iters=iters, inits=inits, mat_sha256=numpy.array(sha(mat)))
+
+    if want("g19"):
+        # the REFINED multi-run: bin/mixemt:311-320 with -M 3 on g13's contributors.  The refinement depends on the reduced
+        # matrix alone, so the first EM is not run again: the contributor table is g13's own.
+        for name in ("pysam", "Bio", "Bio.Seq", "Bio.SeqRecord", "Bio.SeqIO"):
+            sys.modules.setdefault(name, types.ModuleType(name))
+        sys.modules["Bio"].SeqIO = sys.modules["Bio.SeqIO"]
+        sys.modules["Bio.Seq"].Seq = object
+        sys.modules["Bio.SeqRecord"].SeqRecord = object
+        import mixemt.assemble
+        g13 = numpy.load(os.path.join(opts.out, "g13_consumers_multi.npz"))
+        row_ptr, site, obs, who = synth.synth_reads(tables, len(refseq), 600, seed=4)
+        sigs = synth.signatures(tables, row_ptr, site, obs)
+        t0 = time.time()
+        mat = ref.preprocess.build_em_matrix(refseq, phy, sigs, haps, quiet)
+        assert sha(mat) == str(g13["mat_sha256"])
+        wts = numpy.random.default_rng(44).integers(1, 4, size=600).astype(numpy.int64)
+        contribs = [[n, h, float(p)] for n, h, p in zip(str(g13["contrib_names"]).split("\n"),
+                                                        str(g13["contrib_haps"]).split("\n"), g13["contrib_props"])]
+        sub, sub_names = ref.preprocess.reduce_em_matrix(mat, haps, contribs)
+        props, mix, iters, inits = ref_run_em(ref, sub, wts, 23, n_multi=3)
+        print("g19: matrix + refinement x3 %s iterations in %.0f s" % (iters, time.time() - t0), flush=True)
+        refined = ref.assemble.update_contribs([list(c) for c in contribs], (props, mix), sub_names)
+        table = ref.assemble.assign_read_indexes(refined, (props, mix), sub_names, [[str(i)] for i in range(600)], 2.0)
+        names = [c[0] for c in refined]
+        assigned = numpy.full(600, -2, dtype=numpy.int32)
+        for key, idxs in table.items():
+            assigned[sorted(idxs)] = -1 if key == "unassigned" else names.index(key)
+        assert (assigned >= -1).all()
+        with numpy.errstate(divide="ignore", invalid="ignore"):
+            v = numpy.sort(mix - numpy.log(props), axis=1)
+        print("g19: %s; stops %s; props %s (sum %.8f); assigned %s, unassigned %d; closest margin to log 2: %.3f"
+              % (" / ".join(sub_names), [int(v) for v in iters], props, props.sum(), [int((assigned == k).sum()) for k in range(len(names))],
+                 int((assigned < 0).sum()), numpy.abs((v[:, -1] - v[:, -2]) - numpy.log(2.0)).min()), flush=True)
+        save("g19_refine_multi", cols=numpy.array([haps.index(n) for n in sub_names], dtype=numpy.int32), props=props,
+             iters=iters, inits=inits, mix=mix, refined_props=numpy.array([c[2] for c in refined]),
+             contrib_names=numpy.array("\n".join(names)), assigned=assigned, row_ptr=row_ptr, site=site, obs=obs, wts=wts)
 
     if want("g16"):
         for name in ("pysam", "Bio", "Bio.Seq", "Bio.SeqRecord", "Bio.SeqIO"):
