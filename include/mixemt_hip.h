@@ -793,4 +793,5 @@ void mxm_exchange_destroy(mxm_exchange *x);
 /* mixemt's -t tables of a cohort's samples as text, formatted on the device */
 #include "mixemt_hip_stats_samples.h"
 #include "mixemt_hip_samples_runs.h"
+#include "mixemt_hip_bootstrap.h"
 #endif /* MIXEMT_HIP_H */

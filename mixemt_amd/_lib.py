@@ -242,6 +242,19 @@ SAMPLES_RUNS_SIGNATURES = {
                                                      c_ptr]),
 }
 
+# bootstrap replicates of the batched refinement (include/mixemt_hip_bootstrap.h: additions behind ABI version 603); their
+# refusals are pinned in tests/test_bootstrap_host.py
+BOOTSTRAP_SIGNATURES = {
+    "mxm_bootstrap_workspace_bytes": (c_size, [c_i64, c_i32, c_i32, c_i32]),
+    "mxm_bootstrap_weights": (ctypes.c_int, [ctypes.POINTER(Coded), c_ptr, c_i32, c_i32, c_ptr, ctypes.c_uint64, c_ptr, c_ptr,
+                                             c_ptr, c_ptr, c_size, c_ptr]),
+    "mxm_em_loop_samples_narrow_boot": (ctypes.c_int, [ctypes.POINTER(Coded), c_ptr, c_i32, c_i32, c_i32, c_ptr, c_i32, c_ptr,
+                                                       c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f64, c_i32, c_i32, c_ptr, c_ptr,
+                                                       c_size, c_ptr, ctypes.POINTER(EmState)]),
+    "mxm_bootstrap_summary": (ctypes.c_int, [c_i32, c_i32, c_i32, c_ptr, c_ptr, c_ptr, c_f64, c_f64, c_ptr, c_ptr, c_ptr, c_ptr,
+                                             c_ptr, c_ptr, c_ptr]),
+}
+
 # the MXM_VERSION of include/mixemt_hip.h these signatures were written for; load() refuses any other
 ABI_VERSION = 603
 
@@ -280,7 +293,8 @@ def load():
                              "`python -m mixemt_amd.build --force`" % (LIB_PATH, have, ABI_VERSION))
     for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(FINISH_SIGNATURES.items())
                                       + list(VARCHECK_SIGNATURES.items()) + list(ASSEMBLE_SAMPLES_SIGNATURES.items())
-                                      + list(STATS_SAMPLES_SIGNATURES.items()) + list(SAMPLES_RUNS_SIGNATURES.items())):
+                                      + list(STATS_SAMPLES_SIGNATURES.items()) + list(SAMPLES_RUNS_SIGNATURES.items())
+                                      + list(BOOTSTRAP_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:

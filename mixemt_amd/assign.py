@@ -1174,3 +1174,168 @@ def assign_reads_many(cols_list, finished, reads_list, args, pileup=None, max_by
                               max(base, 1))
     aln_sample = torch.from_numpy(numpy.repeat(numpy.arange(n, dtype=numpy.int32), numpy.diff(aln0))).to(dev)
     return CohortContribReads(cols_list, joined, aln0, lab0, names, keys, labels, aln_sample, dcols, frag_d, max_bytes)
+
+
+# ---- bootstrap intervals for the refined proportions of a cohort (no counterpart in the reference) -----------------------------
+BOOTSTRAP_MAX = 4096                # MXM_BOOTSTRAP_MAX of include/mixemt_hip_bootstrap.h: replicates per sample (a cap)
+BOOTSTRAP_BYTES = 4 << 30           # default budget for the replicates' weights, linearised matrices and tables: a cap, not a
+                                    # measurement
+
+
+BOOTSTRAP_REFUSED = {1: "its weights are not non-negative integers",          # state[s].error of mxm_bootstrap_weights
+                     2: "its weights sum to 0 or to 2^31 and more: a total in [1, 2^31) is needed"}
+
+
+def _bootstrap_skip(sample, finished_one, max_rows):
+    """Why bootstrap_many leaves a sample out (None: it takes part), decided on the host.  sample = (matrix, weights).
+    Weights that are a device tensor are NOT read back here: mxm_bootstrap_weights checks them where they are, and
+    bootstrap_many skips the sample on its error code."""
+    refined = finished_one.get("refined")
+    if refined is None:
+        return "no refined result (args.refine_ests off, or nothing contributes)"
+    n_con = len(finished_one["contribs"])
+    if n_con < 1 or n_con > FINISH_KMAX or len(finished_one["sub_haps"]) != n_con:
+        return "%d contributors over %d columns: 1 .. %d, each a column of its own, are taken" % (
+            n_con, len(finished_one["sub_haps"]), FINISH_KMAX)
+    if sample[0].n_rows > max_rows:
+        return "%d rows, more than max_rows = %d" % (sample[0].n_rows, max_rows)
+    wts = sample[1]
+    on_device = hasattr(wts, "is_cuda") and wts.is_cuda
+    if (int(wts.numel()) if on_device else numpy.asarray(wts).size) != sample[0].n_rows:
+        raise ValueError("bootstrap_many: weights do not match the samples' rows")
+    if on_device:
+        return None
+    wts = numpy.asarray(wts, dtype=numpy.float64).reshape(-1)
+    if not (numpy.all(numpy.isfinite(wts)) and numpy.all(wts >= 0) and numpy.all(wts == numpy.floor(wts))):
+        return BOOTSTRAP_REFUSED[1]
+    if not 0 < wts.sum() < 2.0 ** 31:
+        return BOOTSTRAP_REFUSED[2]
+    return None
+
+
+def _bootstrap_check(samples, haplogroups):
+    """bootstrap_many's check of the matrices (host only), as finish_many makes it for its own."""
+    from .preprocess import CodedMatrix
+    mats = [pair[0] for pair in samples]
+    if any(not isinstance(m, CodedMatrix) for m in mats) or any(m.rec.data_ptr() != mats[0].rec.data_ptr() for m in mats):
+        raise ValueError("bootstrap_many: the samples must be views of ONE record buffer (preprocess.build_em_records_many's "
+                         "matrix and cm.rows(lo, hi) of it), as finish_many takes them")
+    if mats[0].n_haps != len(haplogroups):
+        raise ValueError("bootstrap_many: %d haplogroups for matrices of %d columns" % (len(haplogroups), mats[0].n_haps))
+
+
+def bootstrap_many(samples, finished, haplogroups, args, n_boot=1000, seed=0, level=0.95, max_rows=None,
+                   max_bytes=BOOTSTRAP_BYTES, sample_ids=None):
+    """
+    Percentile bootstrap intervals for the refined proportions of the samples of one finish_many call, all replicates of
+    all samples in batched device passes (include/mixemt_hip_bootstrap.h) -- opt-in; the reference has no counterpart.
+    A replicate resamples the sample's N_s reads with replacement (a multinomial draw over the de-duplicated rows by their
+    weights: mxm_bootstrap_weights) and runs the refinement EM on the sample's reduced matrix under the resampled weights
+    (mxm_em_loop_samples_narrow_boot), started at log(refined["props"]) -- the point estimate, NOT a fresh random start:
+    the interval is CONDITIONAL on the detected contributor set and on the mode the point estimate sits in.
+    samples, finished: finish_many's arguments and its result list; haplogroups as there.  args: tolerance, max_iter.
+    n_boot: 2 .. 4096 replicates per sample.  level: the interval's coverage in (0, 1): lo / hi are the quantiles at
+        (1 - level) / 2 and (1 + level) / 2 (numpy.quantile's "linear").
+    seed, sample_ids: the draws of replicate b of sample s depend on (seed, sample_ids[s], b) alone; sample_ids defaults to
+        the sample's index in this call, so pass ids of your own where a sample must keep its draws across calls.
+    max_rows: as finish_many's (default FINISH_MAX_ROWS).  max_bytes: the call refuses up front when the replicates'
+        weights, the linearised matrices and the tables need more.
+    A sample takes part when it has a `refined` result, 1 .. 16 contributors (each a column of its own), at most max_rows
+    rows and non-negative integer weights with a total in [1, 2^31) (weights on the host are checked there, a device tensor
+    by mxm_bootstrap_weights where it is).  Everything that can be refused on the host is refused before a device is asked
+    for.  Returns (boots, skipped): boots[s] is None for every other sample and skipped holds its (s, reason), in sample
+    order; otherwise a dict:
+        columns     the reduced matrix's column names (sub_haps)
+        props_boot  [B][K] the replicates' proportions, in that column order
+        lo, hi, mean, sd   [K] each (sd with ddof = 1); NaN in a column with a replicate that is not finite
+        iters, done [B] each: the replicates' EM steps and stops.  done = 2 is a replicate that ran into args.max_iter: as
+                    run_em reports such a run's proportions, it IS in props_boot and in the four summaries -- look at `done`
+                    where only converged replicates should count
+        intervals   rows [hapNN, haplogroup, proportion, lo, hi, sd] in the order of `contribs`
+        seed, level, n_boot   the call's own values
+    """
+    n = len(samples) if samples else 0
+    if not samples or len(finished) != n:
+        raise ValueError("bootstrap_many: one result of finish_many per sample is needed (%d samples, %d results)"
+                         % (n, len(finished)))
+    if sample_ids is not None and len(sample_ids) != n:
+        raise ValueError("bootstrap_many: sample_ids needs one id per sample (%d samples, %d ids)" % (n, len(sample_ids)))
+    n_boot = int(n_boot)
+    if n_boot < 2 or n_boot > BOOTSTRAP_MAX:
+        raise ValueError("bootstrap_many: n_boot = %d: 2 .. %d replicates are taken" % (n_boot, BOOTSTRAP_MAX))
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError("bootstrap_many: level = %r must lie in (0, 1)" % (level,))
+    ids_all = list(range(n)) if sample_ids is None else [int(i) for i in sample_ids]
+    if any(i < 0 or i >= 2 ** 32 for i in ids_all):
+        raise ValueError("bootstrap_many: sample_ids must be 32-bit unsigned integers")
+    max_rows = FINISH_MAX_ROWS if max_rows is None else int(max_rows)
+    boots, skipped = [None] * n, []
+    hap_index = {}
+    for i, hap in enumerate(haplogroups):
+        hap_index.setdefault(hap, i)
+    ids, plans = [], []
+    for s in range(n):
+        why = _bootstrap_skip(samples[s], finished[s], max_rows)
+        if why is None:
+            plan = _finish_columns(finished[s]["contribs"], hap_index)
+            if len(set(plan[0])) != len(plan[0]) or list(plan[2]) != list(finished[s]["sub_haps"]) \
+                    or len(finished[s]["refined"]["props"]) != len(plan[0]):
+                why = "a haplogroup named twice: its reduced matrix has fewer columns than contributors"
+        if why is None:
+            ids.append(s)
+            plans.append(plan)
+        else:
+            skipped.append((s, why))
+    if not ids:
+        return boots, skipped
+    _bootstrap_check([samples[s] for s in ids], haplogroups)
+    ld, cols, ncol, _ = _finish_tables(plans)
+    rows = [samples[s][0].n_rows for s in ids]
+    total, tables = sum(rows), len(ids) * n_boot * ld
+    spills = any(r * int(k) > 9216 for r, k in zip(rows, ncol))
+    need = 8 * n_boot * total + (8 * total * ld if spills else 0) + (4 * 8 + 24) * tables + 8 * total * ld
+    need += 4 * min(n_boot, 64) * (total + 32 * len(ids))     # (the workspace's counters: at most 32 spare rows per sample)
+    if need > int(max_bytes):
+        raise ValueError("bootstrap_many: %d replicates of %d samples (%d rows) need %d bytes of weights and tables, above the "
+                         "budget of %d bytes (max_bytes): split the cohort or lower n_boot"
+                         % (n_boot, len(ids), total, need, int(max_bytes)))
+
+    dev = require_gpu()
+    wts_d = {s: as_device(samples[s][1], torch.float64, dev).reshape(-1) for s in ids}
+    while True:
+        batch = _finish_batch(samples, wts_d, ids)
+        wb, errors = batch.boot_weights(n_boot, seed, [ids_all[s] for s in ids])
+        if not any(errors):
+            break
+        # device weights that the entry refused: those samples are skipped, the others drawn again without them (their
+        # draws depend on their ids, not on the batch)
+        skipped = sorted(skipped + [(s, BOOTSTRAP_REFUSED.get(e, "mxm_bootstrap_weights: error %d" % e))
+                                    for s, e in zip(ids, errors) if e])
+        keep = [j for j, e in enumerate(errors) if not e]
+        ids, plans = [ids[j] for j in keep], [plans[j] for j in keep]
+        if not ids:
+            return boots, skipped
+        ld, cols, ncol, _ = _finish_tables(plans)
+    mat = batch.gather(cols, ncol, ld)
+    starts = [numpy.asarray(finished[s]["refined"]["props"], dtype=numpy.float64).reshape(-1) for s in ids]
+    _, ln_new, _, state, states = batch.em_loop_boot(mat, ld, ncol, wb, n_boot, starts, args.tolerance, args.max_iter)
+    q_lo, q_hi = (1.0 - float(level)) / 2.0, (1.0 + float(level)) / 2.0
+    x, lo, hi, mean, sd, _ = batch.boot_summary(n_boot, ld, ncol, ln_new, state, q_lo, q_hi)
+    for j, s in enumerate(ids):
+        k = int(ncol[j])
+        column = {name: i for i, name in enumerate(plans[j][2])}
+        rows_out = []
+        for con in finished[s]["contribs"]:
+            i = column[con[1]]
+            rows_out.append([con[0], con[1], con[2], float(lo[j, i]), float(hi[j, i]), float(sd[j, i])])
+        boots[s] = {"columns": list(plans[j][2]), "props_boot": x[j, :, :k].copy(), "lo": lo[j, :k].copy(), "hi": hi[j, :k].copy(),
+                    "mean": mean[j, :k].copy(), "sd": sd[j, :k].copy(), "iters": numpy.array([st[1] for st in states[j]]),
+                    "done": numpy.array([st[0] for st in states[j]]), "intervals": rows_out, "seed": seed, "level": level,
+                    "n_boot": n_boot}
+    return boots, skipped
+
+
+def bootstrap(cm, wts, finished_one, haplogroups, args, **kwargs):
+    """bootstrap_many for ONE sample: (its dict or None, the skip reason or None)."""
+    boots, skipped = bootstrap_many([(cm, wts)], [finished_one], haplogroups, args, **kwargs)
+    return boots[0], (skipped[0][1] if skipped else None)

@@ -30,6 +30,7 @@
 //   fused_narrow_kernels.hpp  em_fused_narrow_kernel (the same for the refinement EM's few columns: the matrix in registers)
 //   samples_finish_kernels.hpp  votes, column gather, refinement EM loop and read assignment of many samples per launch
 //   samples_runs_kernels.hpp    their forms for samples of several EM runs (the fold of the runs' posteriors)
+//   bootstrap_kernels.hpp       bootstrap replicates of the refinement loop: resampled weights, the loop, the summary
 //   samples_kernels.hpp em_iter_samples_kernel, samples_colreduce_kernel (the EM iteration of many samples in one launch: a tile of
 //                       one sample's rows per workgroup)
 //   aln_encode.hpp      HOST code: mxm_aln_encode, the batched alignment front end (process_reads + reduce_reads + row order)
@@ -80,6 +81,7 @@
 #include "samples_kernels.hpp"
 #include "samples_finish_kernels.hpp"
 #include "samples_runs_kernels.hpp"
+#include "bootstrap_kernels.hpp"
 #include "exchange.hpp"
 #include "aln_walk.hpp"
 #include "observe_kernels.hpp"
@@ -2045,12 +2047,14 @@ extern "C" size_t mxm_samples_workspace_bytes(int64_t n_tiles, int32_t S, int32_
 }
 
 // Everything the two entry points refuse before they touch the device; *n_tiles_out = the plan's size.
-static int samples_check(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, const char *who, int64_t *n_tiles_out) {
+// has_width false: an entry that reads no record and so takes no H (mxm_bootstrap_weights).
+static int samples_check(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, const char *who, int64_t *n_tiles_out,
+                         bool has_width = true) {
     if (c == nullptr || row0_host == nullptr || S < 1 || S > 65535)
         return fail(-1, "%s: bad arguments (S = %d; 1 .. 65535 samples)", who, S);
     if (c->R <= 0 || c->rec == nullptr || c->rec_off == nullptr || c->ndist == nullptr)
         return fail(-1, "%s: coded matrix arrays missing (rows %lld)", who, (long long)c->R);
-    if ((H & 1) != 0 || H < 66 || H > 8192) return fail(-1, "%s: H = %d: an even width in [66, 8192] is required", who, H);
+    if (has_width && ((H & 1) != 0 || H < 66 || H > 8192)) return fail(-1, "%s: H = %d: an even width in [66, 8192] is required", who, H);
     if (c->qrec != nullptr) return fail(-1, "%s: a quad dictionary is attached; the batched pass reads the records only", who);
     if (c->R_rest != 0) return fail(-1, "%s: %lld rows without a record (the dense rest): such a sample runs on its own", who, (long long)c->R_rest);
     if (c->n_wide < 0 || (c->n_wide > 0 && c->wide_rows == nullptr)) return fail(-1, "%s: n_wide > 0 needs wide_rows", who);
@@ -2428,19 +2432,22 @@ extern "C" int mxm_votes_samples_runs(const mxm_coded *c, const int64_t *row0_ho
     return 0;
 }
 
-extern "C" int mxm_em_loop_samples_narrow_runs(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, int32_t B,
-                                               const double *M, int32_t ld, const int32_t *ncol_host, const double *w,
-                                               double *props_cur, double *ln_cur, double *ln_new, mxm_em_state *state, double tol,
-                                               int32_t max_iter, int32_t check_every, double *E, void *ws, size_t ws_bytes,
-                                               void *stream, mxm_em_state *state_host) {
-    MXM_ENTER();
+// The loop of B entries per sample, one workgroup per (sample, entry): the runs of mixemt_hip_samples_runs.h (boot false:
+// every entry under the sample's own weights w [R]) or the replicates of mixemt_hip_bootstrap.h (boot true: entry (s, b)
+// under w [B * row0[s] + b * R_s ...], which is then required).  The two differ in the kernel's weight pointer alone.
+static int boot_check(const char *who, int32_t B);
+static int boot_ws_check(const char *who, const void *ws, size_t ws_bytes, int64_t n_tiles, int32_t S, int32_t B, int32_t ld);
+static int narrow_entries_loop(const char *who, bool boot, const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, int32_t B,
+                               const double *M, int32_t ld, const int32_t *ncol_host, const double *w, double *props_cur,
+                               double *ln_cur, double *ln_new, mxm_em_state *state, double tol, int32_t max_iter,
+                               int32_t check_every, double *E, void *ws, size_t ws_bytes, void *stream, mxm_em_state *state_host) {
     int64_t n_tiles = 0;
-    RC_TRY(samples_check(c, row0_host, S, H, "mxm_em_loop_samples_narrow_runs", &n_tiles));
-    RC_TRY(runs_check("mxm_em_loop_samples_narrow_runs", B));
-    if (M == nullptr || props_cur == nullptr || ln_cur == nullptr || ln_new == nullptr || state == nullptr || state_host == nullptr)
-        return fail(-1, "mxm_em_loop_samples_narrow_runs: bad arguments");
-    RC_TRY(finish_cols_check("mxm_em_loop_samples_narrow_runs", S, H, ld, ncol_host, nullptr, nullptr));
-    RC_TRY(runs_ws_check("mxm_em_loop_samples_narrow_runs", ws, ws_bytes, n_tiles, S, B, ld));
+    RC_TRY(samples_check(c, row0_host, S, H, who, &n_tiles));
+    RC_TRY(boot ? boot_check(who, B) : runs_check(who, B));
+    if ((boot && w == nullptr) || M == nullptr || props_cur == nullptr || ln_cur == nullptr || ln_new == nullptr || state == nullptr || state_host == nullptr)
+        return fail(-1, "%s: bad arguments", who);
+    RC_TRY(finish_cols_check(who, S, H, ld, ncol_host, nullptr, nullptr));
+    RC_TRY(boot ? boot_ws_check(who, ws, ws_bytes, n_tiles, S, B, ld) : runs_ws_check(who, ws, ws_bytes, n_tiles, S, B, ld));
     // the linearised samples: in each workgroup's LDS where they fit, else in the global copy E, formed once below
     int64_t lds_doubles = 0;
     bool spills = false;
@@ -2450,7 +2457,7 @@ extern "C" int mxm_em_loop_samples_narrow_runs(const mxm_coded *c, const int64_t
         else spills = true;
     }
     if (spills && E == nullptr)
-        return fail(-1, "mxm_em_loop_samples_narrow_runs: a sample of more than %d cells needs the global copy E", SFIN_LDS_DOUBLES);
+        return fail(-1, "%s: a sample of more than %d cells needs the global copy E", who, SFIN_LDS_DOUBLES);
     if (check_every < 1) check_every = 1;
     if (T.progress != nullptr && check_every > T.progress_every) check_every = T.progress_every;
     hipStream_t s = (hipStream_t)stream;
@@ -2461,8 +2468,10 @@ extern "C" int mxm_em_loop_samples_narrow_runs(const mxm_coded *c, const int64_t
     (void)dispatch_width<SFIN_KMAX>((int)ld, [&](auto n) {
         constexpr int LD = decltype(n)::value;
         if constexpr (LD == 4 || LD == 8 || LD == 16)
-            lds_rc = dynamic_lds_ok(reinterpret_cast<const void *>(&em_loop_samples_narrow_runs_kernel<LD>), lds,
-                                    "em_loop_samples_narrow_runs_kernel");
+            lds_rc = boot ? dynamic_lds_ok(reinterpret_cast<const void *>(&em_loop_samples_narrow_boot_kernel<LD>), lds,
+                                           "em_loop_samples_narrow_boot_kernel")
+                          : dynamic_lds_ok(reinterpret_cast<const void *>(&em_loop_samples_narrow_runs_kernel<LD>), lds,
+                                           "em_loop_samples_narrow_runs_kernel");
     });
     RC_TRY(lds_rc);
     auto launch = [&](int chunk, bool linearise) -> int {
@@ -2474,6 +2483,10 @@ extern "C" int mxm_em_loop_samples_narrow_runs(const mxm_coded *c, const int64_t
                     hipLaunchKernelGGL((linearise_samples_runs_kernel<LD>), dim3((unsigned)n_tiles), dim3(64), 0, s, M,
                                        (const mxm_sample_tile *)L.tiles, (const int64_t *)L.row0, (const int32_t *)L.ncol,
                                        (int)SFIN_LDS_DOUBLES, E);
+                else if (boot)
+                    hipLaunchKernelGGL((em_loop_samples_narrow_boot_kernel<LD>), dim3((unsigned)n_entries), dim3(SFIN_THREADS), lds, s,
+                                       M, E, w, (const int64_t *)L.row0, (const int32_t *)L.ncol, (int)B, ln_cur, ln_new, props_cur,
+                                       state, tol, (int)max_iter, chunk, (int)lds_doubles);
                 else
                     hipLaunchKernelGGL((em_loop_samples_narrow_runs_kernel<LD>), dim3((unsigned)n_entries), dim3(SFIN_THREADS), lds, s,
                                        M, E, w, (const int64_t *)L.row0, (const int32_t *)L.ncol, (int)B, ln_cur, ln_new, props_cur,
@@ -2481,7 +2494,7 @@ extern "C" int mxm_em_loop_samples_narrow_runs(const mxm_coded *c, const int64_t
                 launched = true;
             }
         });
-        if (!launched) return fail(-1, "mxm_em_loop_samples_narrow_runs: ld = %d has no kernel instance", ld);
+        if (!launched) return fail(-1, "%s: ld = %d has no kernel instance", who, ld);
         HIP_TRY(hipGetLastError());
         return 0;
     };
@@ -2499,6 +2512,16 @@ extern "C" int mxm_em_loop_samples_narrow_runs(const mxm_coded *c, const int64_t
         if (T.progress != nullptr) T.progress(state_host, n_entries, T.progress_user);
     }
     return 0;
+}
+
+extern "C" int mxm_em_loop_samples_narrow_runs(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, int32_t B,
+                                               const double *M, int32_t ld, const int32_t *ncol_host, const double *w,
+                                               double *props_cur, double *ln_cur, double *ln_new, mxm_em_state *state, double tol,
+                                               int32_t max_iter, int32_t check_every, double *E, void *ws, size_t ws_bytes,
+                                               void *stream, mxm_em_state *state_host) {
+    MXM_ENTER();
+    return narrow_entries_loop("mxm_em_loop_samples_narrow_runs", false, c, row0_host, S, H, B, M, ld, ncol_host, w, props_cur, ln_cur,
+                               ln_new, state, tol, max_iter, check_every, E, ws, ws_bytes, stream, state_host);
 }
 
 extern "C" int mxm_assign_reads_samples_runs(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, int32_t B,
@@ -2529,6 +2552,125 @@ extern "C" int mxm_assign_reads_samples_runs(const mxm_coded *c, const int64_t *
         }
     });
     if (!launched) return fail(-1, "mxm_assign_reads_samples_runs: ld = %d has no kernel instance", ld);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- bootstrap replicates of the refinement loop (bootstrap_kernels.hpp; include/mixemt_hip_bootstrap.h) ----
+// scratch layout: [the one-run layout][cum, rows x u32][ntot, S x i64][sid, S x u32][cnt, min(B, 64) x rows x u32] with
+// rows = n_tiles x MXM_SAMPLES_TILE_ROWS, the most rows a plan of n_tiles tiles can hold
+struct boot_ws {
+    uint32_t *cum, *sid, *cnt;
+    int64_t *ntot;
+    int64_t rows;
+    size_t bytes;
+};
+static boot_ws boot_layout(void *ws, int64_t n_tiles, int S, int B, int ld) {
+    auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    boot_ws L;
+    char *base = static_cast<char *>(ws);
+    size_t at = finish_layout(nullptr, n_tiles, S, ld).bytes;
+    L.rows = n_tiles * MXM_SAMPLES_TILE_ROWS;
+    L.cum = reinterpret_cast<uint32_t *>(base + at);
+    at += up((size_t)L.rows * sizeof(uint32_t));
+    L.ntot = reinterpret_cast<int64_t *>(base + at);
+    at += up((size_t)S * sizeof(int64_t));
+    L.sid = reinterpret_cast<uint32_t *>(base + at);
+    at += up((size_t)S * sizeof(uint32_t));
+    L.cnt = reinterpret_cast<uint32_t *>(base + at);
+    at += up((size_t)std::min(B, BOOT_CHUNK) * (size_t)L.rows * sizeof(uint32_t));
+    L.bytes = at;
+    return L;
+}
+static bool boot_ok(int32_t B) { return B >= 2 && B <= MXM_BOOTSTRAP_MAX; }
+static int boot_check(const char *who, int32_t B) {
+    if (!boot_ok(B)) return fail(-1, "%s: B = %d replicates per sample: 2 .. %d are taken", who, B, MXM_BOOTSTRAP_MAX);
+    return 0;
+}
+extern "C" size_t mxm_bootstrap_workspace_bytes(int64_t n_tiles, int32_t S, int32_t B, int32_t ld) {
+    if (!boot_ok(B) || n_tiles <= 0 || S <= 0 || ld < 0) return 0;
+    return boot_layout(nullptr, n_tiles, (int)S, (int)B, (int)ld).bytes;
+}
+static int boot_ws_check(const char *who, const void *ws, size_t ws_bytes, int64_t n_tiles, int32_t S, int32_t B, int32_t ld) {
+    if (ws == nullptr || ws_bytes < mxm_bootstrap_workspace_bytes(n_tiles, S, B, ld) || (reinterpret_cast<uintptr_t>(ws) & 15))
+        return fail(-1, "%s: workspace too small (or not 16-byte aligned)", who);
+    return 0;
+}
+
+extern "C" int mxm_bootstrap_weights(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t B, const double *w, uint64_t seed,
+                                     const uint32_t *s_id_host, double *wb, mxm_em_state *state, void *ws, size_t ws_bytes,
+                                     void *stream) {
+    MXM_ENTER();
+    int64_t n_tiles = 0;
+    RC_TRY(samples_check(c, row0_host, S, 0, "mxm_bootstrap_weights", &n_tiles, false));
+    RC_TRY(boot_check("mxm_bootstrap_weights", B));
+    if (w == nullptr || s_id_host == nullptr || wb == nullptr || state == nullptr)
+        return fail(-1, "mxm_bootstrap_weights: bad arguments (w, s_id_host, wb and state are required)");
+    RC_TRY(boot_ws_check("mxm_bootstrap_weights", ws, ws_bytes, n_tiles, S, B, 0));
+    hipStream_t s = (hipStream_t)stream;
+    const finish_ws F = finish_layout(ws, n_tiles, (int)S, 0);
+    const boot_ws L = boot_layout(ws, n_tiles, (int)S, (int)B, 0);
+    // which route the samples take: LDS up to the header's row limit (the batch asks for what its largest such sample needs)
+    int64_t lds_rows = 0;
+    bool large = false;
+    for (int32_t i = 0; i < S; ++i) {
+        const int64_t n = row0_host[i + 1] - row0_host[i];
+        if (n <= BOOT_LDS_ROWS) lds_rows = std::max(lds_rows, n);
+        else large = true;
+    }
+    const size_t lds = (size_t)lds_rows * 2 * sizeof(uint32_t);
+    RC_TRY(dynamic_lds_ok(reinterpret_cast<const void *>(&boot_draw_kernel<false>), lds, "boot_draw_kernel"));
+    RC_TRY(finish_upload(row0_host, (int)S, n_tiles, 0, nullptr, nullptr, nullptr, F, s));
+    static thread_local std::vector<uint32_t> sid;
+    sid.assign(s_id_host, s_id_host + (size_t)S);
+    HIP_TRY(hipMemcpyAsync(L.sid, sid.data(), sid.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(boot_prefix_kernel, dim3((unsigned)S), dim3(BOOT_THREADS), 0, s, w, (const int64_t *)F.row0, L.cum, L.ntot, state);
+    HIP_TRY(hipGetLastError());
+    if (lds_rows > 0) {
+        hipLaunchKernelGGL((boot_draw_kernel<false>), dim3((unsigned)B, (unsigned)S), dim3(BOOT_THREADS), lds, s, (const int64_t *)F.row0,
+                           (const uint32_t *)L.cum, (const int64_t *)L.ntot, (const uint32_t *)L.sid, seed, (int)B, 0, L.cnt, L.rows, wb);
+        HIP_TRY(hipGetLastError());
+    }
+    for (int b0 = 0; large && b0 < B; b0 += BOOT_CHUNK) {    // the counters of BOOT_CHUNK replicates at a time
+        hipLaunchKernelGGL((boot_draw_kernel<true>), dim3((unsigned)std::min(BOOT_CHUNK, (int)B - b0), (unsigned)S), dim3(BOOT_THREADS), 0, s,
+                           (const int64_t *)F.row0, (const uint32_t *)L.cum, (const int64_t *)L.ntot, (const uint32_t *)L.sid, seed,
+                           (int)B, b0, L.cnt, L.rows, wb);
+        HIP_TRY(hipGetLastError());
+    }
+    return 0;
+}
+
+extern "C" int mxm_em_loop_samples_narrow_boot(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, int32_t B,
+                                               const double *M, int32_t ld, const int32_t *ncol_host, const double *wb,
+                                               double *props_cur, double *ln_cur, double *ln_new, mxm_em_state *state, double tol,
+                                               int32_t max_iter, int32_t check_every, double *E, void *ws, size_t ws_bytes,
+                                               void *stream, mxm_em_state *state_host) {
+    MXM_ENTER();
+    return narrow_entries_loop("mxm_em_loop_samples_narrow_boot", true, c, row0_host, S, H, B, M, ld, ncol_host, wb, props_cur, ln_cur,
+                               ln_new, state, tol, max_iter, check_every, E, ws, ws_bytes, stream, state_host);
+}
+
+extern "C" int mxm_bootstrap_summary(int32_t S, int32_t B, int32_t ld, const int32_t *ncol_host, const double *ln_new,
+                                     const mxm_em_state *state, double q_lo, double q_hi, double *x, double *lo, double *hi,
+                                     double *mean, double *sd, int32_t *flag, void *stream) {
+    MXM_ENTER();
+    if (S < 1 || S > 65535) return fail(-1, "mxm_bootstrap_summary: bad arguments (S = %d; 1 .. 65535 samples)", S);
+    RC_TRY(boot_check("mxm_bootstrap_summary", B));
+    RC_TRY(finish_cols_check("mxm_bootstrap_summary", S, 0, ld, ncol_host, nullptr, nullptr));
+    if (!(q_lo >= 0.0 && q_lo <= 1.0 && q_hi >= 0.0 && q_hi <= 1.0))
+        return fail(-1, "mxm_bootstrap_summary: the quantiles %g and %g must lie in [0, 1]", q_lo, q_hi);
+    if (ln_new == nullptr || state == nullptr || x == nullptr || lo == nullptr || hi == nullptr || mean == nullptr || sd == nullptr ||
+        flag == nullptr)
+        return fail(-1, "mxm_bootstrap_summary: bad arguments");
+    hipStream_t s = (hipStream_t)stream;
+    static thread_local std::vector<int32_t> ncol;          // (the call's own copy, as finish_upload keeps one)
+    ncol.assign(ncol_host, ncol_host + (size_t)S);
+    HIP_TRY(hipMemcpyAsync(flag, ncol.data(), ncol.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    hipLaunchKernelGGL(boot_summary_kernel, dim3((unsigned)ld, (unsigned)S), dim3(BOOT_THREADS), 0, s, (int)B, (int)ld,
+                       (const int32_t *)flag, ln_new, state, q_lo, q_hi, x, lo, hi, mean, sd);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(boot_flag_kernel, dim3((unsigned)((S + BOOT_THREADS - 1) / BOOT_THREADS)), dim3(BOOT_THREADS), 0, s, (int)S, (int)ld,
+                       (const double *)lo, flag);
     HIP_TRY(hipGetLastError());
     return 0;
 }

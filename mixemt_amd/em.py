@@ -835,6 +835,9 @@ class SampleFinish(object):
     votes_runs / em_loop_runs / assign_runs are the same stages for samples of B EM runs each (mxm_votes_samples_runs,
     mxm_em_loop_samples_narrow_runs, mxm_assign_reads_samples_runs): per-run tables [S][B][...], the vote and the assignment
     over the runs' posteriors folded in run order (em.py:145-161), one workgroup per (sample, run) in the loop.
+    boot_weights / em_loop_boot / boot_summary are the bootstrap of the refinement (mxm_bootstrap_weights,
+    mxm_em_loop_samples_narrow_boot, mxm_bootstrap_summary; assign.bootstrap_many drives them): B replicates per sample
+    under resampled row weights, one workgroup per (sample, replicate) in the loop.
     """
     KMAX = 16
     LDS_CELLS = 9216                # cells (R_s x ncol) up to which the refinement loops linearise a sample in LDS
@@ -1032,6 +1035,79 @@ class SampleFinish(object):
                                                           self.ws.data_ptr(), ws_bytes, current_stream()),
                    "mxm_assign_reads_samples_runs")
         return assigned, post
+
+    # ---- bootstrap replicates of the refinement (include/mixemt_hip_bootstrap.h): per-replicate tables are [S][B][...] ----
+    def _boot_ws(self, n_boot, ld):
+        """The workspace for B replicates per sample (mxm_bootstrap_workspace_bytes): the object's own, grown if need be."""
+        need = int(self.lib.mxm_bootstrap_workspace_bytes(self.n_tiles, self.n_entries, n_boot, ld))
+        if need == 0:
+            raise ValueError("the bootstrap takes 2 .. 4096 replicates per sample, not %d" % n_boot)
+        if need > self.ws_bytes:
+            self.ws_bytes = need
+            self.ws = torch.empty(need // 8 + 2, dtype=torch.float64, device=self.dev)
+        return need
+
+    def boot_weights(self, n_boot, seed, sample_ids):
+        """The multinomial resamples of the samples' weights (mxm_bootstrap_weights): wb [R * B] on the device, entry
+        B * row0[s] + b * R_s + i, and the samples' error codes [S] (0 fine; 1 a weight that is no non-negative integer;
+        2 a total of 0 or of 2^31 and more -- such a sample's wb is NaN)."""
+        n = self.n_entries
+        ids = numpy.ascontiguousarray(sample_ids, dtype=numpy.uint32)
+        if ids.shape != (n,):
+            raise ValueError("sample_ids must hold %d ids" % n)
+        ws_bytes = self._boot_ws(n_boot, 0)
+        wb = device_empty((self.n_rows * n_boot,), torch.float64, self.dev, "the replicates' weights")
+        state = new_state(n, self.dev)
+        _lib.check(self.lib.mxm_bootstrap_weights(ctypes.byref(self.coded), self.row0_ptr, n, n_boot, self.wts.data_ptr(),
+                                                  int(seed) & 0xFFFFFFFFFFFFFFFF, ids.ctypes.data_as(ctypes.c_void_p),
+                                                  wb.data_ptr(), state.data_ptr(), self.ws.data_ptr(), ws_bytes,
+                                                  current_stream()), "mxm_bootstrap_weights")
+        raw = state.cpu().numpy().tobytes()
+        return wb, [int(st.error) for st in (_lib.EmState * n).from_buffer_copy(raw)]
+
+    def em_loop_boot(self, mat, ld, ncol, wb, n_boot, inits, tolerance, max_iter, check_every=16):
+        """em_loop under every replicate's weights, one workgroup per (sample, replicate) (mxm_em_loop_samples_narrow_boot):
+        inits[s] = [ncol[s]] linear, the start of ALL the sample's replicates.  Returns (ln_cur, ln_new) [S * B][ld] and the
+        states [S * B] ON THE DEVICE (boot_summary reads them there), props_cur likewise, and [(done, iters, l1)] per
+        sample, one list of B each."""
+        n = self.n_entries
+        ncol_h, ncol_p = self._i32(ncol)
+        p0 = numpy.zeros((n, n_boot, ld), dtype=numpy.float64)
+        for s in range(n):
+            p0[s, :, :ncol_h[s]] = numpy.asarray(inits[s], dtype=numpy.float64).reshape(1, ncol_h[s])
+        ln0, p0 = log_inits(p0.reshape(n * n_boot, ld))
+        ws_bytes = self._boot_ws(n_boot, ld)
+        props_cur = torch.from_numpy(p0).to(self.dev)
+        ln_cur = torch.from_numpy(ln0).to(self.dev)
+        ln_new = ln_cur.clone()
+        state = new_state(n * n_boot, self.dev)
+        host_state = (_lib.EmState * (n * n_boot))()
+        spills = any(int(self.row0[s + 1] - self.row0[s]) * int(ncol_h[s]) > self.LDS_CELLS for s in range(n))
+        lin = device_empty((self.n_rows, ld), torch.float64, self.dev, "the linearised reduced matrices") if spills else None
+        _lib.check(self.lib.mxm_em_loop_samples_narrow_boot(ctypes.byref(self.coded), self.row0_ptr, n, self.n_haps, n_boot,
+                                                            mat.data_ptr(), ld, ncol_p, wb.data_ptr(), props_cur.data_ptr(),
+                                                            ln_cur.data_ptr(), ln_new.data_ptr(), state.data_ptr(),
+                                                            float(tolerance), int(max_iter), int(check_every), ptr(lin),
+                                                            self.ws.data_ptr(), ws_bytes, current_stream(), host_state),
+                   "mxm_em_loop_samples_narrow_boot")
+        states = [(st.done, st.iters, st.l1) for st in host_state]
+        return ln_cur, ln_new, props_cur, state, [states[s * n_boot:(s + 1) * n_boot] for s in range(n)]
+
+    def boot_summary(self, n_boot, ld, ncol, ln_new, state, q_lo, q_hi):
+        """The replicates' proportions and their summary per (sample, column) (mxm_bootstrap_summary): ln_new [S * B][ld]
+        and state [S * B] on the device, as em_loop_boot returns them.  Returns numpy arrays: x [S][B][ld] (pad columns
+        0), lo / hi / mean / sd [S][ld] (pad columns NaN) and flag [S] (a replicate of the sample was not usable)."""
+        n = self.n_entries
+        ncol_h, ncol_p = self._i32(ncol)
+        x = torch.zeros((n, n_boot, ld), dtype=torch.float64, device=self.dev)
+        table = torch.full((4, n, ld), float("nan"), dtype=torch.float64, device=self.dev)
+        flag = torch.zeros(n, dtype=torch.int32, device=self.dev)
+        _lib.check(self.lib.mxm_bootstrap_summary(n, n_boot, ld, ncol_p, ln_new.data_ptr(), state.data_ptr(), float(q_lo),
+                                                  float(q_hi), x.data_ptr(), table[0].data_ptr(), table[1].data_ptr(),
+                                                  table[2].data_ptr(), table[3].data_ptr(), flag.data_ptr(), current_stream()),
+                   "mxm_bootstrap_summary")
+        table_h = table.cpu().numpy()
+        return x.cpu().numpy(), table_h[0], table_h[1], table_h[2], table_h[3], flag.cpu().numpy()
 
 
 def _fold_runs(ln_next):

@@ -193,6 +193,28 @@ def report_contributors_many(out, contribs_list, cohort, titles=None):
                 out.write("%s\t%s\t%.4f\t%d\n" % (hap_id, haplogroup, prop, total_reads))
 
 
+def report_intervals_many(out, finished, boots, titles=None):
+    """
+    The bootstrap intervals of a cohort (assign.bootstrap_many's list `boots` beside finish_many's `finished`), sample
+    after sample: one tab-separated line 'hapNN<TAB>haplogroup<TAB>proportion<TAB>lo<TAB>hi<TAB>sd' per contributor, the
+    numbers as report_contributors writes a proportion ('%.4f'; 'nan' for a column whose replicates were not all usable).
+    A sample without intervals (boots[s] is None) gets its contributors' lines with NA in the last three fields.
+    titles: one per sample, written as '# title' ahead of the sample's lines.
+    """
+    n = len(finished)
+    if len(boots) != n or (titles is not None and len(titles) != n):
+        raise ValueError("report_intervals_many: one bootstrap result (and one title) per sample is needed")
+    for s in range(n):
+        if titles is not None:
+            out.write("# %s\n" % (titles[s],))
+        if boots[s] is None:
+            for hap_id, haplogroup, prop in finished[s]["contribs"]:
+                out.write("%s\t%s\t%.4f\tNA\tNA\tNA\n" % (hap_id, haplogroup, prop))
+        else:
+            for hap_id, haplogroup, prop, lo, hi, sd in boots[s]["intervals"]:
+                out.write("%s\t%s\t%.4f\t%.4f\t%.4f\t%.4f\n" % (hap_id, haplogroup, prop, lo, hi, sd))
+
+
 def _stats_block_plan(contribs_list, cohort):
     """
     The obs.tab blocks of every sample, host only: per sample None (no contributors: the reference has no threshold and
