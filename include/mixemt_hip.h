@@ -392,8 +392,9 @@ int mxm_row_argmax_votes_coded(const mxm_coded *c, int32_t H, int32_t n_runs, co
 /* mxm_em_step for coded rows -- em.py:80-83 (mode 0 store) and :156 (mode 1 logaddexp fold):
  *   out[r][h] = (ln_props[h] + M[r][h]) - (rowmax[r] + log(sum_h props[h] * P[r][h]))
  * the row's log-sum-exp taken in the loop's own linear variables (props = exp(ln_props), rowmax from the encoder);
- * a row whose linear sum is 0 or not finite (every supported haplogroup underflowed) is redone in log space with a
- * max shift, so the result is finite exactly where mxm_em_step's is.
+ * a row whose linear sum is below 2^-960 or not finite (every supported haplogroup underflowed, or is so close to it
+ * that the sum is subnormal or made of gradually underflowing products) is redone in log space with a max shift, so the
+ * result is finite exactly where mxm_em_step's is, and as accurate; a row with a normal sum is unaffected.
  * The rows without a record (ndist[r] == 0) come from M_rest[n_rest][ldm_rest], their LOG values, row i of it being
  * row rest_rows[i] of the matrix (n_rest = 0: none; they are then left untouched): the reference's E-step in log
  * space (mxm_em_step's generic kernel) / a plain gather, written to their own rows of `out`. */
@@ -516,7 +517,8 @@ int mxm_em_step(const double *M, int64_t ldm, const double *w,
 int mxm_log_normalize(const double *colsum, int32_t H, double *ln_new,
                       void *stream);
 
-/* l1_out[0] = sum_h |exp(a[h]) - exp(b[h])|   (em.py:53-54) */
+/* l1_out[0] = sum_h |exp(a[h]) - exp(b[h])|   (em.py:53-54); each term is formed as exp(hi) * -expm1(lo - hi), so two
+ * nearly equal entries do not cancel */
 int mxm_l1_exp_diff(const double *a, const double *b, int32_t H,
                     double *l1_out, void *stream);
 

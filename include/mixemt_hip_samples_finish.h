@@ -50,7 +50,8 @@ extern "C" {
  *       mxm_em_loop_samples_narrow blocks the calling thread (one read-back of the states per launch); state_host[S]
  *       receives the final states.
  *   mxm_assign_reads_samples   assemble.py:284-334 per row under its sample's columns: X_c = (ln_theta[s][c] + M[r][c]) -
- *       (rowmax_r + log sum_c props[s][c] exp(M[r][c] - rowmax_r)) as mxm_em_step documents it (or minus lse[r] when lse is
+ *       (rowmax_r + log sum_c props[s][c] exp(M[r][c] - rowmax_r)) as mxm_em_step documents it -- redone in log space with
+ *       a max shift where that sum is below 2^-960 or not finite, as mxm_em_step_coded does -- (or minus lse[r] when lse is
  *       given: the first EM's full-width normaliser, for the unrefined assignment), v_c = X_c - log_props[s][c] (the
  *       returned theta_{k+1}); assigned[r] = perm_host[s][c] of the best c when it beats the runner-up by log_min_fold,
  *       else -1; exactly equal values: the later column wins, as in mxm_assign_reads.  Samples with ncol <= 1 get 0

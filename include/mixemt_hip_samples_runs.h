@@ -30,8 +30,8 @@ extern "C" {
  * returned.  The loop entry is the exception: see its own paragraph.  None of the three is meant to be captured.
  *   mxm_votes_samples_runs   assemble.py:115-123 over the folded posterior of em.py:145-161 (one workgroup per tile of
  *       the plan, then one per sample).  For a row r of sample s: lse_b = the row normaliser under run b's props /
- *       ln_props [S][B][H] (rowmax[r] + log sum_h props[s][b][h] P[r][h], redone in log space where that sum is 0 or not
- *       finite, as mxm_em_step_coded does); v_h = the fold over b, in run order starting from run 0, of
+ *       ln_props [S][B][H] (rowmax[r] + log sum_h props[s][b][h] P[r][h], redone in log space where that sum is below
+ *       2^-960 or not finite, as mxm_em_step_coded does); v_h = the fold over b, in run order starting from run 0, of
  *       logaddexp((ln_props[s][b][h] + M[r][h]) - lse_b); best[r] = the first index of the maximum, a NaN winning
  *       (numpy.argmax) -- the arithmetic of mxm_row_argmax_votes_coded with n_runs = B on the sample's own records, row
  *       for row (the - log B of em.py:161 shifts every column alike and drops out).  votes / counts (nullable) / first /
@@ -53,7 +53,7 @@ extern "C" {
  *   mxm_assign_reads_samples_runs   assemble.py:284-334 per row under the folded posterior of its sample's B runs.
  *       ln_theta / props [S][B][ld] (log theta_k of run b and its exponential), log_props [S][ld] (the log of the
  *       FOLDED proportions the caller reports: run_em's geometric mean).  Per row: L_b = the row normaliser of run b
- *       exactly as mxm_assign_reads_samples forms it for one run, its all-underflowed log-space redo included -- or
+ *       exactly as mxm_assign_reads_samples forms it for one run, its log-space redo of an underflowing sum included -- or
  *       lse[r * B + b] when lse [R][B] is given (the first EM's full-width normalisers, for the unrefined assignment);
  *       X_c = the fold over b, in run order, of logaddexp((ln_theta[s][b][c] + M[r][c]) - L_b), then + (-log B) as ONE
  *       addition (mxm_add_scalar in the per-sample path); v_c = X_c - log_props[s][c].  Best / runner-up /

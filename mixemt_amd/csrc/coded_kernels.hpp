@@ -788,9 +788,10 @@ __global__ __launch_bounds__(256) void decode_rows_kernel(const uint8_t *__restr
 // Log-sum-exp of a coded row under one proportion vector, lse_r = logsumexp_h(ln_props[h] + M[r][h]) (em.py:82), for a
 // workgroup of 256 that holds the row's tables in LDS (s_p = P table, s_m = log table).  Fast form, in the loop's own
 // variables: rowmax_r + log(sum_h props[h] P[r][h]) -- one lookup and one FMA per cell, one logarithm per row.  Where
-// that sum is 0 or not finite (every supported haplogroup's proportion or P underflowed, or a NaN proportion) the
-// row is redone in log space with a max shift, as the dense pass (mxm_em_step) and the reference do, so the records
-// posterior stays finite exactly where theirs does.  Uniform result; contains barriers.
+// that sum is below MXM_LSE_LINEAR_MIN = 2^-960 (common.hpp: zero, subnormal, or formed from gradually underflowing
+// terms -- every supported haplogroup's proportion or P underflowed or is about to) or not finite (a NaN proportion)
+// the row is redone in log space with a max shift, as the dense pass (mxm_em_step) and the reference do, so the records
+// posterior stays finite exactly where theirs does and as accurate.  Uniform result; contains barriers.
 __device__ __forceinline__ double coded_row_lse(const uint8_t *codes, bool wide, const double *s_p, const double *s_m,
                                                 const double *__restrict__ props, const double *__restrict__ ln_props,
                                                 double rowmax_r, int H, double *s_red) {
@@ -802,7 +803,7 @@ __device__ __forceinline__ double coded_row_lse(const uint8_t *codes, bool wide,
     if (lane == 0) s_red[wv] = z;
     __syncthreads();
     z = (s_red[0] + s_red[1]) + (s_red[2] + s_red[3]);
-    if (z > 0.0 && z < INFINITY) return rowmax_r + log(z);  // uniform branch
+    if (lse_linear_ok(z)) return rowmax_r + log(z);         // uniform branch
     double m = -INFINITY;
     for (int h = t; h < H; h += 256) m = fmax(m, ln_props[h] + s_m[rec_code_at(codes, h, wide)]);
     m = wave_max(m);

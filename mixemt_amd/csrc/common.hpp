@@ -190,6 +190,19 @@ __device__ __forceinline__ void group_ratio_to_sgpr(const double *red, int lane,
     for (int g = 0; g < N; ++g) c[g] = readlane_f64(v, g * NW);
 }
 
+// Smallest linear row sum z = sum_h props[h] P[r][h] (P = exp(M - rowmax) <= 1) that the row normalisers taken in linear
+// variables (coded_row_lse, assign_samples_kernel, assign_samples_runs_kernel) trust; below it, as for z == 0 or a z that
+// is not finite, the row is redone in log space with a max shift.  Why: between 0 and 2^-1022 the sum is positive but
+// subnormal -- a few mantissa bits, log(z) wrong from its first decimals on (tests/test_gpu_accuracy_consumers.py, the
+// orphan rows; tests/test_exact_consumers.py restates the old condition as a mutant) -- and a little above
+// it the TERMS still underflow gradually.  The whole damage is absolute: each of the H products is rounded to a multiple
+// of 2^-1074 (error <= 2^-1075), and a subnormal props[h] = exp(ln_props[h]) carries the same rounding times P <= 1, so
+// |z - exact| <= H 2^-1074 + the usual H u z.  With z >= 2^-960 the first term is at most H 2^-114 relative: below
+// u = 2^-53 by a factor 2^61 / H, i.e. for any H an int32 holds.  A row with a normal sum (every golden) keeps its bits.
+#define MXM_LSE_LINEAR_MIN 0x1p-960
+
+__device__ __forceinline__ bool lse_linear_ok(double z) { return z >= MXM_LSE_LINEAR_MIN && z < INFINITY; }   // false for NaN
+
 __device__ __forceinline__ double logaddexp_f64(double a, double b) {
     // numpy.logaddexp semantics (em.py:156)
     if (a == b) return a + 0.693147180559945309417232121458176568;   // covers +-inf ties

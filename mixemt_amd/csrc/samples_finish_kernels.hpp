@@ -355,7 +355,7 @@ __global__ __launch_bounds__(64) void assign_samples_kernel(
 #pragma unroll
         for (int k = 0; k < LD; ++k) z = fma((k < K) ? props[so + k] : 0.0, exp(x[k] - shift), z);
         lse = shift + log(z);
-        if (!(z > 0.0 && z < INFINITY)) {                   // every column underflowed: in log space, as mxm_em_step does
+        if (!lse_linear_ok(z)) {                            // the columns underflow (common.hpp): in log space, as mxm_em_step does
             double mm = -INFINITY;
 #pragma unroll
             for (int k = 0; k < LD; ++k)
