@@ -796,4 +796,6 @@ void mxm_exchange_destroy(mxm_exchange *x);
 #include "mixemt_hip_stats_samples.h"
 #include "mixemt_hip_samples_runs.h"
 #include "mixemt_hip_bootstrap.h"
+/* nested-model fits of the refinement EM over column subsets, and their log-likelihoods */
+#include "mixemt_hip_support.h"
 #endif /* MIXEMT_HIP_H */

@@ -255,6 +255,17 @@ BOOTSTRAP_SIGNATURES = {
                                              c_ptr, c_ptr, c_ptr]),
 }
 
+# nested-model fits of the batched refinement over column masks (include/mixemt_hip_support.h: additions behind ABI version
+# 603); their refusals are pinned in tests/test_support_host.py
+SUPPORT_SIGNATURES = {
+    "mxm_support_workspace_bytes": (c_size, [c_i64, c_i32, c_i32, c_i32]),
+    "mxm_em_loop_samples_narrow_masks": (ctypes.c_int, [ctypes.POINTER(Coded), c_ptr, c_i32, c_i32, c_i32, c_ptr, c_i32, c_ptr,
+                                                        c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_f64, c_i32, c_i32, c_ptr,
+                                                        c_ptr, c_size, c_ptr, ctypes.POINTER(EmState)]),
+    "mxm_loglik_samples_masks": (ctypes.c_int, [ctypes.POINTER(Coded), c_ptr, c_i32, c_i32, c_i32, c_ptr, c_i32, c_ptr, c_ptr,
+                                                c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
+}
+
 # the MXM_VERSION of include/mixemt_hip.h these signatures were written for; load() refuses any other
 ABI_VERSION = 603
 
@@ -294,7 +305,7 @@ def load():
     for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(FINISH_SIGNATURES.items())
                                       + list(VARCHECK_SIGNATURES.items()) + list(ASSEMBLE_SAMPLES_SIGNATURES.items())
                                       + list(STATS_SAMPLES_SIGNATURES.items()) + list(SAMPLES_RUNS_SIGNATURES.items())
-                                      + list(BOOTSTRAP_SIGNATURES.items())):
+                                      + list(BOOTSTRAP_SIGNATURES.items()) + list(SUPPORT_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:

@@ -1213,15 +1213,15 @@ def _bootstrap_skip(sample, finished_one, max_rows):
     return None
 
 
-def _bootstrap_check(samples, haplogroups):
-    """bootstrap_many's check of the matrices (host only), as finish_many makes it for its own."""
+def _bootstrap_check(samples, haplogroups, who="bootstrap_many"):
+    """bootstrap_many's (and support_many's) check of the matrices (host only), as finish_many makes it for its own."""
     from .preprocess import CodedMatrix
     mats = [pair[0] for pair in samples]
     if any(not isinstance(m, CodedMatrix) for m in mats) or any(m.rec.data_ptr() != mats[0].rec.data_ptr() for m in mats):
-        raise ValueError("bootstrap_many: the samples must be views of ONE record buffer (preprocess.build_em_records_many's "
-                         "matrix and cm.rows(lo, hi) of it), as finish_many takes them")
+        raise ValueError("%s: the samples must be views of ONE record buffer (preprocess.build_em_records_many's "
+                         "matrix and cm.rows(lo, hi) of it), as finish_many takes them" % who)
     if mats[0].n_haps != len(haplogroups):
-        raise ValueError("bootstrap_many: %d haplogroups for matrices of %d columns" % (len(haplogroups), mats[0].n_haps))
+        raise ValueError("%s: %d haplogroups for matrices of %d columns" % (who, len(haplogroups), mats[0].n_haps))
 
 
 def bootstrap_many(samples, finished, haplogroups, args, n_boot=1000, seed=0, level=0.95, max_rows=None,
@@ -1339,3 +1339,239 @@ def bootstrap(cm, wts, finished_one, haplogroups, args, **kwargs):
     """bootstrap_many for ONE sample: (its dict or None, the skip reason or None)."""
     boots, skipped = bootstrap_many([(cm, wts)], [finished_one], haplogroups, args, **kwargs)
     return boots[0], (skipped[0][1] if skipped else None)
+
+
+# ---- contributor support: nested-model fits over subsets of the reduced matrix (no counterpart in the reference) ---------------
+SUPPORT_MAX_FITS = 256              # MXM_SUPPORT_MAX_FITS of include/mixemt_hip_support.h: fits per sample (a cap: 2^8 - 1 subsets)
+SUPPORT_ALL_KMAX = 8                # models="all" enumerates 2^K - 1 subsets: refused above this many contributors
+SUPPORT_BYTES = 4 << 30             # default budget for the masks, the tables, the gathered matrices and the fits' E: a cap
+SUPPORT_MAX_ROWS = 100000           # FINISH_MAX_ROWS: one sample of 10^5 rows, every fit through its own slice of E, was measured at
+                                    # 0.34 of the loop of gather / em_loop / logsumexp per (sample, model); nothing larger was
+                                    # measured (profiles/samples/support.md)
+
+
+def _support_skip(sample, finished_one, max_rows):
+    """Why support_many leaves a sample out (None: it takes part), decided on the host: bootstrap_many's rule without the
+    integer-weight condition.  Weights that are a device tensor are not read back."""
+    refined = finished_one.get("refined")
+    if refined is None:
+        return "no refined result (args.refine_ests off, or nothing contributes)"
+    n_con = len(finished_one["contribs"])
+    if n_con < 1 or n_con > FINISH_KMAX or len(finished_one["sub_haps"]) != n_con:
+        return "%d contributors over %d columns: 1 .. %d, each a column of its own, are taken" % (
+            n_con, len(finished_one["sub_haps"]), FINISH_KMAX)
+    if len(set(con[1] for con in finished_one["contribs"])) != n_con:
+        return "a haplogroup named twice: its reduced matrix has fewer columns than contributors"
+    if sample[0].n_rows > max_rows:
+        return "%d rows, more than max_rows = %d" % (sample[0].n_rows, max_rows)
+    wts = sample[1]
+    on_device = hasattr(wts, "is_cuda") and wts.is_cuda
+    if (int(wts.numel()) if on_device else numpy.asarray(wts).size) != sample[0].n_rows:
+        raise ValueError("support_many: weights do not match the samples' rows")
+    if not on_device:
+        wts = numpy.asarray(wts, dtype=numpy.float64).reshape(-1)
+        if not (numpy.all(numpy.isfinite(wts)) and numpy.all(wts >= 0)):
+            return "its weights are not non-negative finite numbers"
+    return None
+
+
+def _support_plan(finished_one, hap_index, models, n_extra, extra, haplogroups=None):
+    """One sample's fits, host only: (cols, names, masks, model_names, extras, truncated).  cols / names: the candidate
+    columns (contributors, then extras) in ASCENDING haplogroup index, as the reduced matrix keeps them; masks[i]: fit i's
+    bits over those columns; model_names[i]: its haplogroups in column order.  vote_order may hold haplogroup indexes (as
+    finish_many returns it: `haplogroups` then names them) or names."""
+    contribs = [con[1] for con in finished_one["contribs"]]
+    explicit = not isinstance(models, str)
+    if extra is not None:
+        wanted = list(extra)
+    elif n_extra and int(n_extra) > 0:
+        voted = [hap if isinstance(hap, str) else haplogroups[int(hap)] for hap in finished_one["vote_order"]]
+        wanted = [hap for hap in voted if hap not in contribs][:int(n_extra)]
+    else:
+        wanted = []
+    if explicit:                                          # a model may name haplogroups beyond the extras: they become extras
+        fits = [tuple(fit) for fit in models]
+        for fit in fits:
+            wanted += [hap for hap in fit if hap not in contribs and hap not in wanted]
+    extras = []
+    for hap in wanted:
+        if hap not in hap_index:
+            raise ValueError("support_many: Unknown haplogroup '%s'" % (hap,))
+        if hap not in contribs and hap not in extras:
+            extras.append(hap)
+    room = FINISH_KMAX - len(contribs)
+    extras, truncated = extras[:room], extras[room:]
+    cand = contribs + extras
+    order = sorted(range(len(cand)), key=lambda k: hap_index[cand[k]])
+    names = [cand[k] for k in order]
+    bit = {hap: i for i, hap in enumerate(names)}
+    full = tuple(contribs)
+    if explicit:
+        for fit in fits:
+            if not fit or len(set(fit)) != len(fit):
+                raise ValueError("support_many: a model needs at least one haplogroup, each named once: %r" % (fit,))
+            gone = [hap for hap in fit if hap not in bit]
+            if gone:
+                raise ValueError("support_many: the model %r needs more than %d candidate columns (%s left out)"
+                                 % (fit, FINISH_KMAX, ", ".join(gone)))
+    elif models == "all":
+        if len(contribs) > SUPPORT_ALL_KMAX:
+            raise ValueError("support_many: models='all' enumerates every subset: at most %d contributors, not %d"
+                             % (SUPPORT_ALL_KMAX, len(contribs)))
+        fits = [full] + [tuple(contribs[i] for i in range(len(contribs)) if (sub >> i) & 1)
+                         for sub in range(1, (1 << len(contribs)) - 1)]
+    elif models in ("drop-one", "add-one"):
+        fits = [full]
+        if len(contribs) > 1:
+            fits += [tuple(hap for hap in contribs if hap != out) for out in contribs]
+        if models == "add-one":
+            fits += [full + (hap,) for hap in extras]
+    else:
+        raise ValueError("support_many: models must be 'drop-one', 'add-one', 'all' or a list of name tuples per sample, "
+                         "not %r" % (models,))
+    masks = [sum(1 << bit[hap] for hap in fit) for fit in fits]
+    model_names = [tuple(hap for hap in names if hap in fit) for fit in fits]
+    return [hap_index[hap] for hap in names], names, masks, model_names, extras, truncated
+
+
+def support_lrt_p(lrt):
+    """The p-value of a likelihood-ratio statistic for ONE proportion tested at the boundary p_k = 0: under the null the
+    statistic follows the mixture 1/2 chi2_0 + 1/2 chi2_1 (Self & Liang 1987), so p = 1/2 P(chi2_1 > lrt) =
+    1/2 erfc(sqrt(max(lrt, 0) / 2)); lrt <= 0 gives 0.5."""
+    import math
+    return 0.5 * math.erfc(math.sqrt(max(float(lrt), 0.0) / 2.0))
+
+
+def support_many(samples, finished, haplogroups, args, models="drop-one", n_extra=0, extra=None, max_rows=None,
+                 max_bytes=SUPPORT_BYTES):
+    """
+    Is a reported contributor supported by the data, and did the vote miss one?  For the samples of one finish_many call:
+    refinement fits over SUBSETS of each sample's reduced matrix -- the full contributor set, each contributor left out,
+    optionally each of a few runner-up haplogroups added -- with their maximised log-likelihoods, all fits of all samples
+    in batched device passes (include/mixemt_hip_support.h) -- opt-in; the reference has no counterpart.
+    samples, finished: finish_many's arguments and its result list; haplogroups as there.  args: tolerance, max_iter.
+    models: "drop-one" (the full set and each contributor left out; one contributor: the full fit only), "add-one" (those
+        and the full set with each extra added), "all" (every non-empty subset of the contributors; refused above 8
+        contributors), or a list with, per sample, a list of tuples of haplogroup names.
+    extra: per sample a list of haplogroup names; else the extras are the first n_extra haplogroups of
+        finished[s]["vote_order"] that are not contributors.  Contributors plus extras are capped at 16 columns; what was
+        cut is reported in `truncated_extras`.
+    Every fit starts UNIFORM over its columns: for fixed components the mixture log-likelihood is concave in the proportions,
+    so the maximum does not depend on the start; no random numbers are drawn and numpy's global stream is not advanced.
+    max_rows: as finish_many's (default SUPPORT_MAX_ROWS).  max_bytes: the call refuses up front when the masks, the
+    tables, the gathered matrices and -- when a sample exceeds the loop's LDS -- the fits' linearised copies need more.
+    A sample takes part when it has a `refined` result, 1 .. 16 contributors (each a column of its own), at most max_rows
+    rows and non-negative finite weights.  Everything that can be refused on the host is refused before a device is asked
+    for.  Returns (support, skipped): support[s] is None for every other sample and skipped holds its (s, reason), in
+    sample order; otherwise a dict:
+        columns     the candidate columns' names, in the gathered matrix's order (ascending haplogroup index)
+        n_eff       the sum of the sample's weights
+        models      per fit a dict: names (in column order), props, loglik, iters, done, bic = -2 ll + (|m| - 1) log n_eff,
+                    aic = -2 ll + 2 (|m| - 1)
+        best_bic    the index in `models` of the smallest bic
+        drop        rows [hapNN, haplogroup, proportion, lrt, p] in the order of `contribs`, lrt = 2 (ll_full - ll_drop),
+                    for every contributor whose drop-one fit (and the full fit) is among the models
+        add         rows [haplogroup, its proportion in the larger fit, lrt, p], lrt = 2 (ll_add - ll_full)
+        truncated_extras   the extras that did not fit the 16 columns
+    p = 1/2 erfc(sqrt(max(lrt, 0) / 2)): the null sits on the boundary p_k = 0, where the statistic follows
+    1/2 chi2_0 + 1/2 chi2_1.  lrt is reported RAW: both fits stop at args.tolerance, not at their maxima, so at a loose
+    tolerance it can come out slightly negative (p is then 0.5).
+    WHAT THE NUMBERS ASSUME: the fragments are treated as independent draws from the mixture; reads that share an error
+    process or a PCR ancestor are not, and lrt then overstates the evidence.  De-duplication does not change ll: a row of
+    weight w counts exactly as w equal rows.
+    """
+    import math
+    n = len(samples) if samples else 0
+    if not samples or len(finished) != n:
+        raise ValueError("support_many: one result of finish_many per sample is needed (%d samples, %d results)"
+                         % (n, len(finished)))
+    explicit = not isinstance(models, str)
+    if explicit and len(models) != n:
+        raise ValueError("support_many: models needs one list of name tuples per sample (%d samples, %d lists)" % (n, len(models)))
+    if extra is not None and len(extra) != n:
+        raise ValueError("support_many: extra needs one list of names per sample (%d samples, %d lists)" % (n, len(extra)))
+    max_rows = SUPPORT_MAX_ROWS if max_rows is None else int(max_rows)
+    support, skipped = [None] * n, []
+    hap_index = {}
+    for i, hap in enumerate(haplogroups):
+        hap_index.setdefault(hap, i)
+    ids, plans = [], []
+    for s in range(n):
+        why = _support_skip(samples[s], finished[s], max_rows)
+        if why is None:
+            ids.append(s)
+            plans.append(_support_plan(finished[s], hap_index, models[s] if explicit else models, n_extra,
+                                       None if extra is None else extra[s], haplogroups))
+        else:
+            skipped.append((s, why))
+    if not ids:
+        return support, skipped
+    n_fits = max(len(plan[2]) for plan in plans)
+    if n_fits > SUPPORT_MAX_FITS:
+        raise ValueError("support_many: %d fits for one sample: 1 .. %d are taken" % (n_fits, SUPPORT_MAX_FITS))
+    _bootstrap_check([samples[s] for s in ids], haplogroups, who="support_many")
+    ld, cols, ncol, _ = _finish_tables([(plan[0], list(range(len(plan[0]))), plan[1]) for plan in plans])
+    masks = numpy.zeros((len(ids), n_fits), dtype=numpy.uint32)
+    for j, plan in enumerate(plans):
+        masks[j, :len(plan[2])] = plan[2]
+    rows = [samples[s][0].n_rows for s in ids]
+    total, tables = sum(rows), len(ids) * n_fits * ld
+    spills = any(r * int(k) > 9216 for r, k in zip(rows, ncol))
+    need = 4 * len(ids) * n_fits + (3 * 8 + 24) * tables + 8 * len(ids) * n_fits + 8 * total * ld
+    need += 8 * n_fits * total * ld if spills else 0
+    if need > int(max_bytes):
+        raise ValueError("support_many: %d fits of %d samples (%d rows) need %d bytes of masks, tables and matrices, above the "
+                         "budget of %d bytes (max_bytes): split the cohort or ask for fewer models"
+                         % (n_fits, len(ids), total, need, int(max_bytes)))
+
+    dev = require_gpu()
+    wts_d = {s: as_device(samples[s][1], torch.float64, dev).reshape(-1) for s in ids}
+    batch = _finish_batch(samples, wts_d, ids)
+    mat = batch.gather(cols, ncol, ld)
+    bits = (masks[:, :, None] >> numpy.arange(ld, dtype=numpy.uint32)[None, None, :]) & 1
+    size = numpy.maximum(bits.sum(axis=2, keepdims=True), 1)
+    starts = [(bits[j] / size[j])[:, :int(ncol[j])] for j in range(len(ids))]
+    _, ln_new, states = batch.em_loop_masks(mat, ld, ncol, masks, starts, args.tolerance, args.max_iter)
+    ll, n_eff = batch.loglik_masks(mat, ld, ncol, masks, ln_new)
+    for j, s in enumerate(ids):
+        _, names, fit_masks, fit_names, extras, truncated = plans[j]
+        column = {hap: i for i, hap in enumerate(names)}
+        fits, index = [], {}
+        for b, fit in enumerate(fit_names):
+            free = len(fit) - 1
+            at = [column[hap] for hap in fit]
+            value = float(ll[j, b])
+            fits.append({"names": fit, "props": numpy.exp(ln_new[j, b, at]), "loglik": value, "iters": int(states[j][b][1]),
+                         "done": int(states[j][b][0]), "bic": -2.0 * value + (free * math.log(float(n_eff[j])) if free else 0.0),
+                         "aic": -2.0 * value + 2.0 * free})
+            index.setdefault(frozenset(fit), b)
+        contribs = finished[s]["contribs"]
+        full = index.get(frozenset(con[1] for con in contribs))
+        drop, add = [], []
+        if full is not None:
+            everyone = frozenset(con[1] for con in contribs)
+            for con in contribs:
+                b = index.get(everyone - {con[1]}) if len(contribs) > 1 else None
+                if b is not None:
+                    lrt = 2.0 * (fits[full]["loglik"] - fits[b]["loglik"])
+                    drop.append([con[0], con[1], con[2], lrt, support_lrt_p(lrt)])
+            for hap in extras:
+                b = index.get(everyone | {hap})
+                if b is not None:
+                    lrt = 2.0 * (fits[b]["loglik"] - fits[full]["loglik"])
+                    add.append([hap, float(fits[b]["props"][fits[b]["names"].index(hap)]), lrt, support_lrt_p(lrt)])
+        support[s] = {"columns": list(names), "n_eff": float(n_eff[j]), "models": fits,
+                      "best_bic": min(range(len(fits)), key=lambda b: (fits[b]["bic"] != fits[b]["bic"], fits[b]["bic"])),
+                      "drop": drop, "add": add, "truncated_extras": list(truncated)}
+    return support, skipped
+
+
+def support(cm, wts, finished_one, haplogroups, args, **kwargs):
+    """support_many for ONE sample: (its dict or None, the skip reason or None).  models / extra, where given as lists, are
+    this sample's own (a list of name tuples; a list of names)."""
+    if "models" in kwargs and not isinstance(kwargs["models"], str):
+        kwargs["models"] = [kwargs["models"]]
+    if kwargs.get("extra") is not None:
+        kwargs["extra"] = [kwargs["extra"]]
+    out, skipped = support_many([(cm, wts)], [finished_one], haplogroups, args, **kwargs)
+    return out[0], (skipped[0][1] if skipped else None)

@@ -31,6 +31,7 @@
 //   samples_finish_kernels.hpp  votes, column gather, refinement EM loop and read assignment of many samples per launch
 //   samples_runs_kernels.hpp    their forms for samples of several EM runs (the fold of the runs' posteriors)
 //   bootstrap_kernels.hpp       bootstrap replicates of the refinement loop: resampled weights, the loop, the summary
+//   support_kernels.hpp         nested-model fits of the refinement loop over column masks, and their log-likelihoods
 //   samples_kernels.hpp em_iter_samples_kernel, samples_colreduce_kernel (the EM iteration of many samples in one launch: a tile of
 //                       one sample's rows per workgroup)
 //   aln_encode.hpp      HOST code: mxm_aln_encode, the batched alignment front end (process_reads + reduce_reads + row order)
@@ -82,6 +83,7 @@
 #include "samples_finish_kernels.hpp"
 #include "samples_runs_kernels.hpp"
 #include "bootstrap_kernels.hpp"
+#include "support_kernels.hpp"
 #include "exchange.hpp"
 #include "aln_walk.hpp"
 #include "observe_kernels.hpp"
@@ -2435,19 +2437,33 @@ extern "C" int mxm_votes_samples_runs(const mxm_coded *c, const int64_t *row0_ho
 // The loop of B entries per sample, one workgroup per (sample, entry): the runs of mixemt_hip_samples_runs.h (boot false:
 // every entry under the sample's own weights w [R]) or the replicates of mixemt_hip_bootstrap.h (boot true: entry (s, b)
 // under w [B * row0[s] + b * R_s ...], which is then required).  The two differ in the kernel's weight pointer alone.
+// NARROW_MASKS: the fits of mixemt_hip_support.h -- entry (s, b) over the columns of mask_host[s * B + b] (0: an unused slot,
+// which never counts as running), its e in its own slice of E [B x R x ld] instead of one linearise pass for all.
+enum narrow_kind { NARROW_RUNS, NARROW_BOOT, NARROW_MASKS };
 static int boot_check(const char *who, int32_t B);
 static int boot_ws_check(const char *who, const void *ws, size_t ws_bytes, int64_t n_tiles, int32_t S, int32_t B, int32_t ld);
-static int narrow_entries_loop(const char *who, bool boot, const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, int32_t B,
+static int support_check(const char *who, int32_t S, int32_t B, const int32_t *ncol_host, const uint32_t *mask_host);
+static int support_ws_check(const char *who, const void *ws, size_t ws_bytes, int64_t n_tiles, int32_t S, int32_t B, int32_t ld);
+static int support_upload_masks(void *ws, int64_t n_tiles, int S, int B, int ld, const uint32_t *mask_host, hipStream_t stream,
+                                const uint32_t **masks_dev);
+static int narrow_entries_loop(const char *who, narrow_kind kind, const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, int32_t B,
                                const double *M, int32_t ld, const int32_t *ncol_host, const double *w, double *props_cur,
                                double *ln_cur, double *ln_new, mxm_em_state *state, double tol, int32_t max_iter,
-                               int32_t check_every, double *E, void *ws, size_t ws_bytes, void *stream, mxm_em_state *state_host) {
+                               int32_t check_every, double *E, void *ws, size_t ws_bytes, void *stream, mxm_em_state *state_host,
+                               const uint32_t *mask_host = nullptr) {
+    const bool boot = kind == NARROW_BOOT, masks = kind == NARROW_MASKS;
     int64_t n_tiles = 0;
     RC_TRY(samples_check(c, row0_host, S, H, who, &n_tiles));
-    RC_TRY(boot ? boot_check(who, B) : runs_check(who, B));
+    if (!masks) RC_TRY(boot ? boot_check(who, B) : runs_check(who, B));
     if ((boot && w == nullptr) || M == nullptr || props_cur == nullptr || ln_cur == nullptr || ln_new == nullptr || state == nullptr || state_host == nullptr)
         return fail(-1, "%s: bad arguments", who);
     RC_TRY(finish_cols_check(who, S, H, ld, ncol_host, nullptr, nullptr));
-    RC_TRY(boot ? boot_ws_check(who, ws, ws_bytes, n_tiles, S, B, ld) : runs_ws_check(who, ws, ws_bytes, n_tiles, S, B, ld));
+    if (masks) {
+        RC_TRY(support_check(who, S, B, ncol_host, mask_host));
+        RC_TRY(support_ws_check(who, ws, ws_bytes, n_tiles, S, B, ld));
+    } else {
+        RC_TRY(boot ? boot_ws_check(who, ws, ws_bytes, n_tiles, S, B, ld) : runs_ws_check(who, ws, ws_bytes, n_tiles, S, B, ld));
+    }
     // the linearised samples: in each workgroup's LDS where they fit, else in the global copy E, formed once below
     int64_t lds_doubles = 0;
     bool spills = false;
@@ -2464,11 +2480,14 @@ static int narrow_entries_loop(const char *who, bool boot, const mxm_coded *c, c
     const finish_ws L = finish_layout(ws, n_tiles, (int)S, (int)ld);
     const size_t lds = (size_t)lds_doubles * sizeof(double);
     const int n_entries = (int)S * (int)B;
+    const uint32_t *masks_dev = nullptr;                    // (NARROW_MASKS: in the workspace, uploaded below)
     int lds_rc = -1;
     (void)dispatch_width<SFIN_KMAX>((int)ld, [&](auto n) {
         constexpr int LD = decltype(n)::value;
         if constexpr (LD == 4 || LD == 8 || LD == 16)
-            lds_rc = boot ? dynamic_lds_ok(reinterpret_cast<const void *>(&em_loop_samples_narrow_boot_kernel<LD>), lds,
+            lds_rc = masks ? dynamic_lds_ok(reinterpret_cast<const void *>(&em_loop_samples_narrow_masks_kernel<LD>), lds,
+                                            "em_loop_samples_narrow_masks_kernel")
+                     : boot ? dynamic_lds_ok(reinterpret_cast<const void *>(&em_loop_samples_narrow_boot_kernel<LD>), lds,
                                            "em_loop_samples_narrow_boot_kernel")
                           : dynamic_lds_ok(reinterpret_cast<const void *>(&em_loop_samples_narrow_runs_kernel<LD>), lds,
                                            "em_loop_samples_narrow_runs_kernel");
@@ -2483,6 +2502,10 @@ static int narrow_entries_loop(const char *who, bool boot, const mxm_coded *c, c
                     hipLaunchKernelGGL((linearise_samples_runs_kernel<LD>), dim3((unsigned)n_tiles), dim3(64), 0, s, M,
                                        (const mxm_sample_tile *)L.tiles, (const int64_t *)L.row0, (const int32_t *)L.ncol,
                                        (int)SFIN_LDS_DOUBLES, E);
+                else if (masks)
+                    hipLaunchKernelGGL((em_loop_samples_narrow_masks_kernel<LD>), dim3((unsigned)n_entries), dim3(SFIN_THREADS), lds, s,
+                                       M, E, w, (const int64_t *)L.row0, (const int32_t *)L.ncol, masks_dev, (int)B, ln_cur, ln_new,
+                                       props_cur, state, tol, (int)max_iter, chunk, (int)lds_doubles);
                 else if (boot)
                     hipLaunchKernelGGL((em_loop_samples_narrow_boot_kernel<LD>), dim3((unsigned)n_entries), dim3(SFIN_THREADS), lds, s,
                                        M, E, w, (const int64_t *)L.row0, (const int32_t *)L.ncol, (int)B, ln_cur, ln_new, props_cur,
@@ -2499,13 +2522,15 @@ static int narrow_entries_loop(const char *who, bool boot, const mxm_coded *c, c
         return 0;
     };
     RC_TRY(finish_upload(row0_host, (int)S, n_tiles, (int)ld, ncol_host, nullptr, nullptr, L, s));
+    if (masks) RC_TRY(support_upload_masks(ws, n_tiles, (int)S, (int)B, (int)ld, mask_host, s, &masks_dev));
     RC_TRY(read_state(state_host, state, n_entries, s));
     auto running = [&]() {
         int n = 0;
-        for (int e = 0; e < n_entries; ++e) n += (state_host[e].done == 0 && ncol_host[e / B] > 0) ? 1 : 0;
+        for (int e = 0; e < n_entries; ++e)
+            n += (state_host[e].done == 0 && ncol_host[e / B] > 0 && (!masks || mask_host[e] != 0)) ? 1 : 0;
         return n;
     };
-    if (spills && max_iter > 0 && running() > 0) RC_TRY(launch(0, true));
+    if (spills && !masks && max_iter > 0 && running() > 0) RC_TRY(launch(0, true));
     while (max_iter > 0 && running() > 0) {
         RC_TRY(launch((int)check_every, false));
         RC_TRY(read_state(state_host, state, n_entries, s));
@@ -2520,7 +2545,7 @@ extern "C" int mxm_em_loop_samples_narrow_runs(const mxm_coded *c, const int64_t
                                                int32_t max_iter, int32_t check_every, double *E, void *ws, size_t ws_bytes,
                                                void *stream, mxm_em_state *state_host) {
     MXM_ENTER();
-    return narrow_entries_loop("mxm_em_loop_samples_narrow_runs", false, c, row0_host, S, H, B, M, ld, ncol_host, w, props_cur, ln_cur,
+    return narrow_entries_loop("mxm_em_loop_samples_narrow_runs", NARROW_RUNS, c, row0_host, S, H, B, M, ld, ncol_host, w, props_cur, ln_cur,
                                ln_new, state, tol, max_iter, check_every, E, ws, ws_bytes, stream, state_host);
 }
 
@@ -2646,7 +2671,7 @@ extern "C" int mxm_em_loop_samples_narrow_boot(const mxm_coded *c, const int64_t
                                                int32_t max_iter, int32_t check_every, double *E, void *ws, size_t ws_bytes,
                                                void *stream, mxm_em_state *state_host) {
     MXM_ENTER();
-    return narrow_entries_loop("mxm_em_loop_samples_narrow_boot", true, c, row0_host, S, H, B, M, ld, ncol_host, wb, props_cur, ln_cur,
+    return narrow_entries_loop("mxm_em_loop_samples_narrow_boot", NARROW_BOOT, c, row0_host, S, H, B, M, ld, ncol_host, wb, props_cur, ln_cur,
                                ln_new, state, tol, max_iter, check_every, E, ws, ws_bytes, stream, state_host);
 }
 
@@ -2671,6 +2696,81 @@ extern "C" int mxm_bootstrap_summary(int32_t S, int32_t B, int32_t ld, const int
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(boot_flag_kernel, dim3((unsigned)((S + BOOT_THREADS - 1) / BOOT_THREADS)), dim3(BOOT_THREADS), 0, s, (int)S, (int)ld,
                        (const double *)lo, flag);
+    HIP_TRY(hipGetLastError());
+    return 0;
+}
+
+// ---- nested-model fits of the refinement loop over column masks (support_kernels.hpp; include/mixemt_hip_support.h) ----
+// scratch layout: [the one-run layout][masks, S x B x u32]
+static bool support_ok(int32_t B) { return B >= 1 && B <= MXM_SUPPORT_MAX_FITS; }
+extern "C" size_t mxm_support_workspace_bytes(int64_t n_tiles, int32_t S, int32_t B, int32_t ld) {
+    if (!support_ok(B) || n_tiles <= 0 || S <= 0 || ld < 0) return 0;
+    return finish_layout(nullptr, n_tiles, (int)S, (int)ld).bytes + (((size_t)S * (size_t)B * sizeof(uint32_t) + 255) & ~(size_t)255);
+}
+// B and the masks: every bit of a mask below the sample's column count (mask 0: an unused slot)
+static int support_check(const char *who, int32_t S, int32_t B, const int32_t *ncol_host, const uint32_t *mask_host) {
+    if (!support_ok(B)) return fail(-1, "%s: B = %d fits per sample: 1 .. %d are taken", who, B, MXM_SUPPORT_MAX_FITS);
+    if (mask_host == nullptr) return fail(-1, "%s: bad arguments (mask_host missing)", who);
+    for (int32_t s = 0; s < S; ++s)
+        for (int32_t b = 0; b < B; ++b) {
+            const uint32_t mask = mask_host[(int64_t)s * B + b];
+            if (((uint64_t)mask >> ncol_host[s]) != 0)
+                return fail(-1, "%s: sample %d, fit %d: mask 0x%x has a bit at or above ncol = %d", who, s, b, mask, ncol_host[s]);
+        }
+    return 0;
+}
+static int support_ws_check(const char *who, const void *ws, size_t ws_bytes, int64_t n_tiles, int32_t S, int32_t B, int32_t ld) {
+    if (ws == nullptr || ws_bytes < mxm_support_workspace_bytes(n_tiles, S, B, ld) || (reinterpret_cast<uintptr_t>(ws) & 15))
+        return fail(-1, "%s: workspace too small (or not 16-byte aligned)", who);
+    return 0;
+}
+// the masks into the workspace behind the one-run layout, from a vector of the call's own (finish_upload says why)
+static int support_upload_masks(void *ws, int64_t n_tiles, int S, int B, int ld, const uint32_t *mask_host, hipStream_t stream,
+                                const uint32_t **masks_dev) {
+    static thread_local std::vector<uint32_t> masks;
+    uint32_t *dev = reinterpret_cast<uint32_t *>(static_cast<char *>(ws) + finish_layout(nullptr, n_tiles, S, ld).bytes);
+    masks.assign(mask_host, mask_host + (size_t)S * B);
+    HIP_TRY(hipMemcpyAsync(dev, masks.data(), masks.size() * sizeof(uint32_t), hipMemcpyHostToDevice, stream));
+    *masks_dev = dev;
+    return 0;
+}
+
+extern "C" int mxm_em_loop_samples_narrow_masks(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, int32_t B,
+                                                const double *M, int32_t ld, const int32_t *ncol_host, const uint32_t *mask_host,
+                                                const double *w, double *props_cur, double *ln_cur, double *ln_new,
+                                                mxm_em_state *state, double tol, int32_t max_iter, int32_t check_every, double *E,
+                                                void *ws, size_t ws_bytes, void *stream, mxm_em_state *state_host) {
+    MXM_ENTER();
+    return narrow_entries_loop("mxm_em_loop_samples_narrow_masks", NARROW_MASKS, c, row0_host, S, H, B, M, ld, ncol_host, w, props_cur,
+                               ln_cur, ln_new, state, tol, max_iter, check_every, E, ws, ws_bytes, stream, state_host, mask_host);
+}
+
+extern "C" int mxm_loglik_samples_masks(const mxm_coded *c, const int64_t *row0_host, int32_t S, int32_t H, int32_t B, const double *M,
+                                        int32_t ld, const int32_t *ncol_host, const uint32_t *mask_host, const double *w,
+                                        const double *ln_props, double *ll, double *n_eff, void *ws, size_t ws_bytes, void *stream) {
+    MXM_ENTER();
+    const char *who = "mxm_loglik_samples_masks";
+    int64_t n_tiles = 0;
+    RC_TRY(samples_check(c, row0_host, S, H, who, &n_tiles));
+    if (M == nullptr || ln_props == nullptr || ll == nullptr || n_eff == nullptr) return fail(-1, "%s: bad arguments", who);
+    RC_TRY(finish_cols_check(who, S, H, ld, ncol_host, nullptr, nullptr));
+    RC_TRY(support_check(who, S, B, ncol_host, mask_host));
+    RC_TRY(support_ws_check(who, ws, ws_bytes, n_tiles, S, B, ld));
+    hipStream_t s = (hipStream_t)stream;
+    const finish_ws L = finish_layout(ws, n_tiles, (int)S, (int)ld);
+    RC_TRY(finish_upload(row0_host, (int)S, n_tiles, (int)ld, ncol_host, nullptr, nullptr, L, s));
+    const uint32_t *masks_dev = nullptr;
+    RC_TRY(support_upload_masks(ws, n_tiles, (int)S, (int)B, (int)ld, mask_host, s, &masks_dev));
+    bool launched = false;
+    (void)dispatch_width<SFIN_KMAX>((int)ld, [&](auto n) {
+        constexpr int LD = decltype(n)::value;
+        if constexpr (LD == 4 || LD == 8 || LD == 16) {
+            hipLaunchKernelGGL((loglik_samples_masks_kernel<LD>), dim3((unsigned)((int)S * (int)B)), dim3(SFIN_THREADS), 0, s, M, w,
+                               (const int64_t *)L.row0, (const int32_t *)L.ncol, masks_dev, (int)B, ln_props, ll, n_eff);
+            launched = true;
+        }
+    });
+    if (!launched) return fail(-1, "%s: ld = %d has no kernel instance", who, ld);
     HIP_TRY(hipGetLastError());
     return 0;
 }

@@ -164,15 +164,22 @@ __global__ __launch_bounds__(SFIN_THREADS) void gather_samples_kernel(
     }
 }
 
+// column k of a K-column row takes part: every k < K, or (MASKED: the fits of support_kernels.hpp) the bits of mask, all of
+// them below K.  A column that does not is a pad column to everything below.
+template <bool MASKED>
+__device__ __forceinline__ bool sfin_col_on(int k, int K, uint32_t mask) {
+    return MASKED ? ((mask >> k) & 1u) != 0 : k < K;
+}
+
 // e[k] = exp(x[k] - rowmax) of one reduced row x [LD] with K columns: 0 in the pad columns, no shift for a row without a
-// finite maximum
-template <int LD>
-__device__ __forceinline__ void sfin_linear_row(const double *__restrict__ row, int K, double (&e)[LD]) {
+// finite maximum (the maximum is over the columns that take part)
+template <int LD, bool MASKED = false>
+__device__ __forceinline__ void sfin_linear_row(const double *__restrict__ row, int K, double (&e)[LD], uint32_t mask = 0) {
     double x[LD];
     double m = -INFINITY;
 #pragma unroll
     for (int k = 0; k < LD; ++k) {
-        x[k] = (k < K) ? row[k] : -INFINITY;
+        x[k] = sfin_col_on<MASKED>(k, K, mask) ? row[k] : -INFINITY;
         m = fmax(m, x[k]);
     }
     const double shift = isfinite(m) ? m : 0.0;
@@ -193,11 +200,13 @@ __device__ __forceinline__ void sfin_linear_row(const double *__restrict__ row, 
 // The loop of ONE workgroup on n rows x K columns: Ms / Es / ws point at the sample's first row, ln_cur / ln_new /
 // props_cur [LD] and st at the entry's own tables.  E_READY: a pass before the launch has formed the sample's e in Es
 // (samples_runs_kernels.hpp: several workgroups share one sample there), so this workgroup only reads it.
-template <int LD, bool E_READY>
+// MASKED (support_kernels.hpp): the fit's columns are the bits of mask instead of all k < K; whether the sample fits LDS
+// is still judged on n x K, and column k keeps its place k * n there.
+template <int LD, bool E_READY, bool MASKED = false>
 __device__ __forceinline__ void sfin_em_loop_body(const double *__restrict__ Ms, double *__restrict__ Es, const double *__restrict__ ws,
                                                   int64_t n, int K, double *__restrict__ ln_cur, double *__restrict__ ln_new,
                                                   double *__restrict__ props_cur, mxm_em_state *__restrict__ st, double tol,
-                                                  int max_iter, int chunk, int lds_doubles) {
+                                                  int max_iter, int chunk, int lds_doubles, uint32_t mask = 0) {
     constexpr int THREADS = SFIN_THREADS, NW = THREADS / 64;
     extern __shared__ double sfin_e[];
     __shared__ double s_red[LD][NW];
@@ -207,11 +216,11 @@ __device__ __forceinline__ void sfin_em_loop_body(const double *__restrict__ Ms,
     // ---- linearise once: e = exp(M - rowmax), pad columns 0 ----
     for (int64_t r = t; r < n && (in_lds || !E_READY); r += THREADS) {
         double e[LD];
-        sfin_linear_row<LD>(Ms + r * LD, K, e);
+        sfin_linear_row<LD, MASKED>(Ms + r * LD, K, e, mask);
 #pragma unroll
         for (int k = 0; k < LD; ++k) {
             if (in_lds) {
-                if (k < K) sfin_e[k * n + r] = e[k];
+                if (sfin_col_on<MASKED>(k, K, mask)) sfin_e[k * n + r] = e[k];
             } else {
                 Es[r * LD + k] = e[k];
             }
@@ -224,8 +233,8 @@ __device__ __forceinline__ void sfin_em_loop_body(const double *__restrict__ Ms,
     double lc[LD], p[LD], ln_next[LD];
 #pragma unroll
     for (int k = 0; k < LD; ++k) {
-        lc[k] = (k < K) ? ln_cur[k] : -INFINITY;
-        p[k] = (k < K) ? (iters > 0 ? props_cur[k] : exp(lc[k])) : 0.0;
+        lc[k] = sfin_col_on<MASKED>(k, K, mask) ? ln_cur[k] : -INFINITY;
+        p[k] = sfin_col_on<MASKED>(k, K, mask) ? (iters > 0 ? props_cur[k] : exp(lc[k])) : 0.0;
         ln_next[k] = lc[k];
     }
     for (int it = 0; it < chunk && done == 0; ++it) {
@@ -235,7 +244,7 @@ __device__ __forceinline__ void sfin_em_loop_body(const double *__restrict__ Ms,
         for (int64_t r = t; r < n; r += THREADS) {
             double e[LD];
 #pragma unroll
-            for (int k = 0; k < LD; ++k) e[k] = in_lds ? ((k < K) ? sfin_e[k * n + r] : 0.0) : Es[r * LD + k];
+            for (int k = 0; k < LD; ++k) e[k] = in_lds ? (sfin_col_on<MASKED>(k, K, mask) ? sfin_e[k * n + r] : 0.0) : Es[r * LD + k];
             double z = 0.0;
 #pragma unroll
             for (int k = 0; k < LD; ++k) z = fma(p[k], e[k], z);
@@ -253,7 +262,7 @@ __device__ __forceinline__ void sfin_em_loop_body(const double *__restrict__ Ms,
 #pragma unroll
         for (int k = 0; k < LD; ++k) {
             double a = 0.0;
-            if (k < K) {
+            if (sfin_col_on<MASKED>(k, K, mask)) {
                 a = s_red[k][0];
 #pragma unroll
                 for (int q = 1; q < NW; ++q) a += s_red[k][q];
@@ -267,7 +276,7 @@ __device__ __forceinline__ void sfin_em_loop_body(const double *__restrict__ Ms,
         double pn[LD];
 #pragma unroll
         for (int k = 0; k < LD; ++k) {
-            if (k < K) {
+            if (sfin_col_on<MASKED>(k, K, mask)) {
                 ln_next[k] = lc[k] + log(T[k]) - ltot;      // em.py:87-89
                 pn[k] = exp(ln_next[k]);
                 l1 += fabs(pn[k] - p[k]);                   // em.py:53-54
@@ -292,7 +301,7 @@ __device__ __forceinline__ void sfin_em_loop_body(const double *__restrict__ Ms,
         if (t == k && k < K) {
             ln_cur[k] = lc[k];
             props_cur[k] = p[k];
-            if (done > 0) ln_new[k] = ln_next[k];
+            if (done > 0 || !sfin_col_on<MASKED>(k, K, mask)) ln_new[k] = ln_next[k];   // (a masked-out column: -inf, 0, -inf)
         }
     }
     if (t == 0) {

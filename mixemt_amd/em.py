@@ -1109,6 +1109,78 @@ class SampleFinish(object):
         table_h = table.cpu().numpy()
         return x.cpu().numpy(), table_h[0], table_h[1], table_h[2], table_h[3], flag.cpu().numpy()
 
+    # ---- nested-model fits over column masks (include/mixemt_hip_support.h): per-fit tables are [S][B][...] ----
+    def _support_ws(self, n_fits, ld):
+        """The workspace for B fits per sample (mxm_support_workspace_bytes): the object's own, grown if need be."""
+        need = int(self.lib.mxm_support_workspace_bytes(self.n_tiles, self.n_entries, n_fits, ld))
+        if need == 0:
+            raise ValueError("the support fits take 1 .. 256 fits per sample, not %d" % n_fits)
+        if need > self.ws_bytes:
+            self.ws_bytes = need
+            self.ws = torch.empty(need // 8 + 2, dtype=torch.float64, device=self.dev)
+        return need
+
+    def _masks(self, masks):
+        arr = numpy.ascontiguousarray(masks, dtype=numpy.uint32)
+        if arr.ndim != 2 or arr.shape[0] != self.n_entries:
+            raise ValueError("masks must be [%d][B]" % self.n_entries)
+        return arr, arr.ctypes.data_as(ctypes.c_void_p)
+
+    def em_loop_masks(self, mat, ld, ncol, masks, inits, tolerance, max_iter, check_every=16):
+        """em_loop over SUBSETS of every sample's columns, one workgroup per (sample, fit)
+        (mxm_em_loop_samples_narrow_masks): masks [S][B] uint32 (bit k = column k of the reduced matrix; 0 = an unused slot,
+        left alone), inits[s] = [B][ncol[s]] linear (only the masked-in entries count).  Returns (ln_cur, ln_new) as
+        [S][B][ld] numpy arrays -- -inf in a masked-out column -- and [(done, iters, l1)] per sample, one list of B each."""
+        n = self.n_entries
+        ncol_h, ncol_p = self._i32(ncol)
+        mask_h, mask_p = self._masks(masks)
+        n_fits = mask_h.shape[1]
+        p0 = numpy.zeros((n, n_fits, ld), dtype=numpy.float64)
+        for s in range(n):
+            p0[s, :, :ncol_h[s]] = numpy.asarray(inits[s], dtype=numpy.float64).reshape(n_fits, ncol_h[s])
+        p0 *= ((mask_h[:, :, None] >> numpy.arange(ld, dtype=numpy.uint32)[None, None, :]) & 1)
+        ln0, p0 = log_inits(p0.reshape(n * n_fits, ld))
+        ws_bytes = self._support_ws(n_fits, ld)
+        props_cur = torch.from_numpy(p0).to(self.dev)
+        ln_cur = torch.from_numpy(ln0).to(self.dev)
+        ln_new = ln_cur.clone()
+        state = new_state(n * n_fits, self.dev)
+        host_state = (_lib.EmState * (n * n_fits))()
+        spills = any(int(self.row0[s + 1] - self.row0[s]) * int(ncol_h[s]) > self.LDS_CELLS for s in range(n))
+        lin = device_empty((n_fits * self.n_rows, ld), torch.float64, self.dev, "the fits' linearised matrices") if spills else None
+        _lib.check(self.lib.mxm_em_loop_samples_narrow_masks(ctypes.byref(self.coded), self.row0_ptr, n, self.n_haps, n_fits,
+                                                             mat.data_ptr(), ld, ncol_p, mask_p, self.wts.data_ptr(),
+                                                             props_cur.data_ptr(), ln_cur.data_ptr(), ln_new.data_ptr(),
+                                                             state.data_ptr(), float(tolerance), int(max_iter), int(check_every),
+                                                             ptr(lin), self.ws.data_ptr(), ws_bytes, current_stream(), host_state),
+                   "mxm_em_loop_samples_narrow_masks")
+        states = [(st.done, st.iters, st.l1) for st in host_state]
+        return (ln_cur.cpu().numpy().reshape(n, n_fits, ld), ln_new.cpu().numpy().reshape(n, n_fits, ld),
+                [states[s * n_fits:(s + 1) * n_fits] for s in range(n)])
+
+    def loglik_masks(self, mat, ld, ncol, masks, ln_props):
+        """The fits' log-likelihoods (mxm_loglik_samples_masks): ll[s][b] = sum_r w_r log sum_{k in mask} p_k exp(M_rk) with
+        p = exp(ln_props[s][b]) (ln_props [S][B][ld], host or device), and n_eff[s] = sum of w.  Returns numpy arrays
+        ll [S][B] (NaN in an unused slot) and n_eff [S]."""
+        n = self.n_entries
+        ncol_h, ncol_p = self._i32(ncol)
+        mask_h, mask_p = self._masks(masks)
+        n_fits = mask_h.shape[1]
+        if isinstance(ln_props, torch.Tensor):
+            lnp = ln_props.to(self.dev, torch.float64).contiguous()
+        else:
+            lnp = torch.from_numpy(numpy.ascontiguousarray(ln_props, dtype=numpy.float64)).to(self.dev)
+        if lnp.numel() != n * n_fits * ld:
+            raise ValueError("ln_props must be [%d][%d][%d]" % (n, n_fits, ld))
+        ws_bytes = self._support_ws(n_fits, ld)
+        ll = torch.full((n, n_fits), float("nan"), dtype=torch.float64, device=self.dev)
+        n_eff = torch.empty(n, dtype=torch.float64, device=self.dev)
+        _lib.check(self.lib.mxm_loglik_samples_masks(ctypes.byref(self.coded), self.row0_ptr, n, self.n_haps, n_fits,
+                                                     mat.data_ptr(), ld, ncol_p, mask_p, self.wts.data_ptr(), lnp.data_ptr(),
+                                                     ll.data_ptr(), n_eff.data_ptr(), self.ws.data_ptr(), ws_bytes,
+                                                     current_stream()), "mxm_loglik_samples_masks")
+        return ll.cpu().numpy(), n_eff.cpu().numpy()
+
 
 def _fold_runs(ln_next):
     """collect_result's proportions: exp(mean of the runs' LOG proportions), in run order (em.py:155, :163)."""

@@ -215,6 +215,34 @@ def report_intervals_many(out, finished, boots, titles=None):
                 out.write("%s\t%s\t%.4f\t%.4f\t%.4f\t%.4f\n" % (hap_id, haplogroup, prop, lo, hi, sd))
 
 
+def report_support_many(out, finished, support, titles=None):
+    """
+    The contributor support of a cohort (assign.support_many's list `support` beside finish_many's `finished`), sample
+    after sample: one tab-separated line 'hapNN<TAB>haplogroup<TAB>proportion<TAB>lrt<TAB>p' per contributor (proportion
+    and lrt as '%.4f', p as '%.3g'; NA NA where the contributor has no drop-one fit -- a sample of one contributor -- or the
+    sample has no support result), then 'add<TAB>haplogroup<TAB>proportion<TAB>lrt<TAB>p' per extra that was added to the
+    full set, then 'best_bic<TAB>name,name,...<TAB>bic' ('%.4f') for the model with the smallest BIC.
+    titles: one per sample, written as '# title' ahead of the sample's lines.
+    """
+    n = len(finished)
+    if len(support) != n or (titles is not None and len(titles) != n):
+        raise ValueError("report_support_many: one support result (and one title) per sample is needed")
+    for s in range(n):
+        if titles is not None:
+            out.write("# %s\n" % (titles[s],))
+        rows = {} if support[s] is None else {row[0]: row for row in support[s]["drop"]}
+        for hap_id, haplogroup, prop in finished[s]["contribs"]:
+            if hap_id in rows:
+                out.write("%s\t%s\t%.4f\t%.4f\t%.3g\n" % (hap_id, haplogroup, prop, rows[hap_id][3], rows[hap_id][4]))
+            else:
+                out.write("%s\t%s\t%.4f\tNA\tNA\n" % (hap_id, haplogroup, prop))
+        if support[s] is not None:
+            for haplogroup, prop, lrt, p_value in support[s]["add"]:
+                out.write("add\t%s\t%.4f\t%.4f\t%.3g\n" % (haplogroup, prop, lrt, p_value))
+            best = support[s]["models"][support[s]["best_bic"]]
+            out.write("best_bic\t%s\t%.4f\n" % (",".join(best["names"]), best["bic"]))
+
+
 def _stats_block_plan(contribs_list, cohort):
     """
     The obs.tab blocks of every sample, host only: per sample None (no contributors: the reference has no threshold and
