@@ -798,4 +798,5 @@ void mxm_exchange_destroy(mxm_exchange *x);
 #include "mixemt_hip_bootstrap.h"
 /* nested-model fits of the refinement EM over column subsets, and their log-likelihoods */
 #include "mixemt_hip_support.h"
+#include "mixemt_hip_detect.h"
 #endif /* MIXEMT_HIP_H */

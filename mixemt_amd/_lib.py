@@ -266,6 +266,16 @@ SUPPORT_SIGNATURES = {
                                                 c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_size, c_ptr]),
 }
 
+# the detection bootstrap's tail: the candidate rule and the variant check over device lists (include/mixemt_hip_detect.h:
+# additions behind ABI version 603); their refusals are pinned in tests/test_detect_host.py
+DETECT_SIGNATURES = {
+    "mxm_detect_candidates": (ctypes.c_int, [c_ptr, c_ptr, c_ptr, c_ptr, c_ptr, c_i32, c_i32, c_f64, c_i32, c_ptr, c_ptr, c_ptr,
+                                             c_ptr]),
+    "mxm_check_variants_entries": (ctypes.c_int, [c_ptr, c_i32, c_i64, c_ptr, c_ptr, c_i32, c_ptr, c_ptr, c_i32, c_i64, c_ptr,
+                                                  c_i32, c_ptr, c_ptr, c_i32, c_f64, c_f64, c_f64, c_i32, c_i32, c_ptr, c_ptr,
+                                                  c_ptr, c_ptr, c_ptr]),
+}
+
 # the MXM_VERSION of include/mixemt_hip.h these signatures were written for; load() refuses any other
 ABI_VERSION = 603
 
@@ -305,7 +315,8 @@ def load():
     for name, (restype, argtypes) in (list(SIGNATURES.items()) + list(FINISH_SIGNATURES.items())
                                       + list(VARCHECK_SIGNATURES.items()) + list(ASSEMBLE_SAMPLES_SIGNATURES.items())
                                       + list(STATS_SAMPLES_SIGNATURES.items()) + list(SAMPLES_RUNS_SIGNATURES.items())
-                                      + list(BOOTSTRAP_SIGNATURES.items()) + list(SUPPORT_SIGNATURES.items())):
+                                      + list(BOOTSTRAP_SIGNATURES.items()) + list(SUPPORT_SIGNATURES.items())
+                                      + list(DETECT_SIGNATURES.items())):
         try:
             fn = getattr(lib, name)
         except AttributeError:

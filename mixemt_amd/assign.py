@@ -1341,6 +1341,381 @@ def bootstrap(cm, wts, finished_one, haplogroups, args, **kwargs):
     return boots[0], (skipped[0][1] if skipped else None)
 
 
+# ---- detection bootstrap: how often each contributor is CALLED under resampled reads (no counterpart in the reference) --------
+DETECT_BYTES = 4 << 30              # default budget for ONE chunk of (sample, replicate) entries: a cap, not a measurement
+DETECT_LD = 64                      # row stride of the candidate tables (the widest the check takes): E x 64 tables leave the device
+DETECT_SETS = 10                    # kept sets listed per sample
+
+
+def _detect_skip(sample, result_one, args):
+    """Why detect_many leaves a sample out (None: it takes part), decided on the host; device weights are left to
+    mxm_bootstrap_weights, as _bootstrap_skip leaves them."""
+    if result_one.get("route") != "batch":
+        return "its first EM did not run in the batch (route %r)" % (result_one.get("route"),)
+    if int(getattr(args, "n_multi", 1)) != 1:
+        return "args.n_multi = %d: one EM run per sample is taken" % int(args.n_multi)
+    if getattr(args, "contributors", None):
+        return "args.contributors is given: there is nothing to detect"
+    wts = sample[1]
+    on_device = hasattr(wts, "is_cuda") and wts.is_cuda
+    if (int(wts.numel()) if on_device else numpy.asarray(wts).size) != sample[0].n_rows:
+        raise ValueError("detect_many: weights do not match the samples' rows")
+    if on_device:
+        return None
+    wts = numpy.asarray(wts, dtype=numpy.float64).reshape(-1)
+    if not (numpy.all(numpy.isfinite(wts)) and numpy.all(wts >= 0) and numpy.all(wts == numpy.floor(wts))):
+        return BOOTSTRAP_REFUSED[1]
+    if not 0 < wts.sum() < 2.0 ** 31:
+        return BOOTSTRAP_REFUSED[2]
+    return None
+
+
+def _detect_entry_bytes(n_rows, n_haps, tile_rows, row_bytes=16):
+    """What ONE (sample, replicate) entry of n_rows rows adds to a chunk: its tiles' partial sums, the vote's tables (24 H),
+    the loop's four tables (32 H), the start's copy and the exponentiated proportions (16 H), `best` and the repeated
+    rec_off / ndist (row_bytes per row together), and the 64-wide tables that leave the device."""
+    n_tiles = (int(n_rows) + tile_rows - 1) // tile_rows
+    return n_tiles * n_haps * 8 + (24 + 32 + 16) * n_haps + (4 + row_bytes) * int(n_rows) + DETECT_LD * 32 + 64
+
+
+DETECT_CHUNK_ENTRIES = 65535        # entries one mxm_em_loop_samples call takes
+
+
+def _detect_chunks(entry_bytes, max_bytes):
+    """Contiguous chunks [e0, e1) of the entries, each within max_bytes (and within the batched loop's 65535 entries);
+    ValueError when one entry does not fit."""
+    chunks, e0, used = [], 0, 0
+    for e, need in enumerate(entry_bytes):
+        if need > max_bytes:
+            raise ValueError("detect_many: one (sample, replicate) entry needs %d bytes, above the budget of %d bytes "
+                             "(max_bytes): split the cohort or lower n_boot" % (need, max_bytes))
+        if used + need > max_bytes or e - e0 >= DETECT_CHUNK_ENTRIES:
+            chunks.append((e0, e))
+            e0, used = e, 0
+        used += need
+    if e0 < len(entry_bytes):
+        chunks.append((e0, len(entry_bytes)))
+    return chunks
+
+
+def _exp_as_run_em_many(ln):
+    """numpy.exp over a CONTIGUOUS copy, as run_em_many exponentiates its log proportions: numpy takes another loop for a
+    strided view, and the two loops need not round alike."""
+    flat = numpy.ascontiguousarray(ln, dtype=numpy.float64)
+    return numpy.exp(flat.reshape(-1)).reshape(flat.shape)
+
+
+DETECT_FAILED = ("the EM loop did not finish", "poisoned: a NaN vote or proportion, or a loop error",
+                 "more than 64 candidates", "the variant check left it alone (ncand)", "a candidate index outside the tree")
+
+
+def _detect_failure(ncand, flag, done):
+    """The reason a replicate is not usable (None: it is), in the order the result documents."""
+    if done == 0:
+        return DETECT_FAILED[0]
+    if ncand < 0:
+        return DETECT_FAILED[1]
+    if ncand > DETECT_LD:
+        return DETECT_FAILED[2]
+    if flag == 1:
+        return DETECT_FAILED[3]
+    if flag != 0:
+        return DETECT_FAILED[4]
+    return None
+
+
+def _detect_summary(cand, ncand, keep, flag, done, contribs, haplogroups, hap_index):
+    """The host summary of ONE sample's replicates: cand [B][ld] / ncand [B] / keep [B][ld] (None: the check is off, every
+    candidate is kept) / flag [B] / done [B] as they left the device; contribs: the point estimate's [[hapNN, haplogroup,
+    proportion], ...].  Returns the dict of detection, n_used, n_failed, set_sizes, same_set, sets (see detect_many)."""
+    n_boot = len(ncand)
+    est = [hap_index[con[1]] for con in contribs]
+    est_prop = {}
+    for con in contribs:
+        est_prop.setdefault(hap_index[con[1]], con[2])
+    n_cand, n_kept = {h: 0 for h in est}, {h: 0 for h in est}
+    failed, sizes, sets, n_used, same = {}, {}, {}, 0, 0
+    for b in range(n_boot):
+        why = _detect_failure(int(ncand[b]), int(flag[b]), int(done[b]))
+        if why is not None:
+            failed[why] = failed.get(why, 0) + 1
+            continue
+        n_used += 1
+        kept = []
+        for i in range(int(ncand[b])):
+            h = int(cand[b][i])
+            n_cand[h] = n_cand.get(h, 0) + 1
+            n_kept.setdefault(h, 0)
+            if keep is None or keep[b][i]:
+                n_kept[h] += 1
+                kept.append(h)
+        key = tuple(sorted(kept))
+        sizes[len(key)] = sizes.get(len(key), 0) + 1
+        sets[key] = sets.get(key, 0) + 1                     # (dict order = first occurrence)
+        same += 1 if set(key) == set(est) and len(key) == len(set(est)) else 0
+    rows = [[haplogroups[h], n_cand[h], n_kept[h], h in est_prop, est_prop.get(h)]
+            for h in sorted(n_cand, key=lambda h: (-n_kept[h], h))]
+    top = sorted(sets.items(), key=lambda kv: -kv[1])[:DETECT_SETS]          # (stable: ties by first occurrence)
+    return {"detection": rows, "n_used": n_used, "n_failed": failed, "set_sizes": dict(sorted(sizes.items())), "same_set": same,
+            "sets": [([haplogroups[h] for h in key], count) for key, count in top]}
+
+
+def detect_many(samples, results, finished, haplogroups, args, n_boot=200, seed=0, level=0.95, obs=None, phylo=None,
+                var_tables=None, sample_ids=None, inits=None, max_bytes=DETECT_BYTES):
+    """
+    A bootstrap of the DETECTION: how often each haplogroup is called a contributor when the sample's reads are drawn
+    again, for the samples of one run_em_many / finish_many call, all replicates in batched device passes -- opt-in; the
+    reference has no counterpart.  Per replicate: the sample's N_s reads are resampled with replacement
+    (mxm_bootstrap_weights), the WIDE EM over all haplogroups runs under the resampled weights (mxm_em_loop_samples; the
+    entries of the batch are (sample, replicate) pairs over the sample's records, offsets repeated, nothing copied), the
+    rows vote (mxm_votes_samples), the candidates are formed on the device (mxm_detect_candidates: args.min_reads, checking
+    order) and, with args.var_check, checked there (mxm_check_variants_entries).  Only 64-wide tables leave the device.
+    WHAT THE FREQUENCIES ARE CONDITIONAL ON: the variant check runs against the OBSERVED pileup -- pileup noise is not
+    resampled -- and every replicate stops by the rule of args.tolerance / args.max_iter from a warm start.  They are NOT
+    the call frequencies of the full pipeline under resampled alignments.
+    samples, results: run_em_many's arguments and results; finished: finish_many's results (its contributors are the point
+        estimate the replicates are compared with).  args: min_reads, var_check (min_var_reads, frac_var_reads, var_fraction,
+        var_count), tolerance, max_iter, n_multi, contributors.
+    n_boot: 2 .. 4096 replicates per sample.  seed, sample_ids: replicate b of sample s depends on (seed, sample_ids[s], b)
+        alone (sample_ids defaults to the index in this call): n_boot = 8 reproduces the replicates of n_boot = 4.
+    inits: None starts every replicate of s at results[s]["props"] renormalised to sum 1 -- for fixed components the wide
+        likelihood is concave in the proportions, so its maximum does not depend on the start; the warm start only shortens
+        the way -- or a list with [H] proportions per sample (None: the default).
+    obs / phylo / var_tables: with args.var_check, obs must be an observe.CohortPileup (table s is sample s's; anything else
+        is a ValueError) and phylo (or var_tables, a VarCheckTables built with a device) is required.
+    level: coverage of lo / hi below.  max_bytes: entries (s, b) are taken in order in contiguous chunks of at most this many
+        bytes (_detect_entry_bytes each); ValueError when one entry does not fit.  The chunking changes no result.
+    A row of resampled weight 0 STAYS in the batch with weight 0: it still counts for `first`.  That differs from deleting
+    the row only between candidates of exactly equal proportions, and for args.min_reads <= 0, where a haplogroup that won
+    only weight-0 rows is a candidate.
+    A sample takes part when results[s]["route"] == "batch", args.n_multi == 1, args.contributors is empty and its weights
+    are non-negative integers with a total in [1, 2^31) (device weights are checked by mxm_bootstrap_weights).  Returns
+    (detect, skipped): detect[s] is None for every other sample and skipped holds its (s, reason); otherwise a dict:
+        detection   rows [haplogroup, n_candidate, n_kept, in_estimate, estimate_prop_or_None] for every haplogroup that is a
+                    candidate in a usable replicate or among finished[s]["contribs"], by descending n_kept, then index;
+                    with the check off n_kept == n_candidate
+        n_used      usable replicates, the denominator: flag == 0, 0 <= ncand <= 64, done != 0; n_failed: {reason: count}
+                    of the others, which appear in no count
+        set_sizes   {size of the kept set: replicates};  same_set: replicates whose kept set is the point estimate's
+        sets        the ten most frequent kept sets as ([haplogroups by index], count), ties by first occurrence
+        columns, props_boot [B][K]   the point estimate's contributors and their WIDE-EM proportions per replicate,
+                    unconditional on the set (NaN for a replicate whose loop did not finish)
+        lo, hi, mean, sd [K]   mxm_bootstrap_summary over props_boot when 1 <= K <= 16; otherwise absent, and
+                    `summary` says why (it is "mxm_bootstrap_summary" when they are there)
+        cand [B][64], ncand [B], keep [B][64], flag [B], cand_props [B][64]   the replicates' own tables (cand_props: exp of
+                    the loop's log theta_{k+1} formed on the host, as run_em_many forms props)
+        iters, done [B]; seed, level, n_boot; var_check: "observed pileup" or "off"
+    """
+    from . import em
+    from .observe import CohortPileup
+    n = len(samples) if samples else 0
+    if not samples or len(results) != n or len(finished) != n:
+        raise ValueError("detect_many: one result of run_em_many and one of finish_many per sample are needed (%d samples, %d and "
+                         "%d results)" % (n, len(results), len(finished) if finished is not None else 0))
+    if sample_ids is not None and len(sample_ids) != n:
+        raise ValueError("detect_many: sample_ids needs one id per sample (%d samples, %d ids)" % (n, len(sample_ids)))
+    if inits is not None and len(inits) != n:
+        raise ValueError("detect_many: inits needs one entry per sample (%d samples, %d entries)" % (n, len(inits)))
+    n_boot = int(n_boot)
+    if n_boot < 2 or n_boot > BOOTSTRAP_MAX:
+        raise ValueError("detect_many: n_boot = %d: 2 .. %d replicates are taken" % (n_boot, BOOTSTRAP_MAX))
+    if not 0.0 < float(level) < 1.0:
+        raise ValueError("detect_many: level = %r must lie in (0, 1)" % (level,))
+    ids_all = list(range(n)) if sample_ids is None else [int(i) for i in sample_ids]
+    if any(i < 0 or i >= 2 ** 32 for i in ids_all):
+        raise ValueError("detect_many: sample_ids must be 32-bit unsigned integers")
+    max_bytes = int(max_bytes)
+    checked = bool(args.var_check)
+    if checked:
+        if not isinstance(obs, CohortPileup):
+            raise ValueError("detect_many: args.var_check needs obs= an observe.CohortPileup (the pileups stay on the device)")
+        if len(obs) != n:
+            raise ValueError("detect_many: obs needs one table per sample (%d samples, %d tables)" % (n, len(obs)))
+        if phylo is None and var_tables is None:
+            raise ValueError("detect_many: the variant check needs phylo= (or var_tables=)")
+        if var_tables is not None and (var_tables.n_haps != len(haplogroups) or var_tables.key_ptr is None):
+            raise ValueError("detect_many: var_tables must be built with a device for the samples' %d haplogroups" % len(haplogroups))
+        if obs.L > VAR_CHECK_MAX_L:
+            raise ValueError("detect_many: a pileup of %d positions: the check kernel takes at most %d" % (obs.L, VAR_CHECK_MAX_L))
+    hap_index = {}
+    for i, hap in enumerate(haplogroups):
+        hap_index.setdefault(hap, i)
+    n_haps = len(haplogroups)
+    detect, skipped, ids = [None] * n, [], []
+    for s in range(n):
+        why = _detect_skip(samples[s], results[s], args)
+        if why is None:
+            ids.append(s)
+        else:
+            skipped.append((s, why))
+    if not ids:
+        return detect, skipped
+    _bootstrap_check([samples[s] for s in ids], haplogroups, who="detect_many")
+    starts = {}
+    for s in ids:
+        start = numpy.asarray(results[s]["props"] if inits is None or inits[s] is None else inits[s], dtype=numpy.float64).reshape(-1)
+        if start.shape != (n_haps,) or not numpy.all(numpy.isfinite(start)) or numpy.any(start < 0) or not start.sum() > 0:
+            raise ValueError("detect_many: the start of sample %d must be %d finite non-negative proportions with a positive sum"
+                             % (s, n_haps))
+        starts[s] = start / start.sum()
+    lib = _lib.load()
+    tile_rows = int(lib.mxm_samples_tile_rows())
+    mat0 = samples[ids[0]][0]
+    row_bytes = mat0.rec_off.element_size() + mat0.ndist.element_size()
+    for s in ids:                                            # (the one-entry refusal needs no device either)
+        need = _detect_entry_bytes(samples[s][0].n_rows, n_haps, tile_rows, row_bytes)
+        if need > max_bytes:
+            _detect_chunks([need], max_bytes)
+
+    dev = require_gpu()
+    if checked:
+        if var_tables is None:
+            var_tables = VarCheckTables.build(phylo, haplogroups, dev)
+        if var_tables is None or var_tables.key_ptr is None:
+            raise ValueError("detect_many: the tree has a derived allele outside ACGT: the device check cannot take it")
+        if var_tables.max_pos >= obs.L:
+            raise ValueError("detect_many: the tree's variants reach past the pileup (L = %d)" % obs.L)
+    wts_d = {s: as_device(samples[s][1], torch.float64, dev).reshape(-1) for s in ids}
+    while True:
+        batch = _finish_batch(samples, wts_d, ids)
+        wb, errors = batch.boot_weights(n_boot, seed, [ids_all[s] for s in ids])
+        if not any(errors):
+            break
+        skipped = sorted(skipped + [(s, BOOTSTRAP_REFUSED.get(e, "mxm_bootstrap_weights: error %d" % e))
+                                    for s, e in zip(ids, errors) if e])
+        ids = [s for s, e in zip(ids, errors) if not e]
+        if not ids:
+            return detect, skipped
+    del batch
+    n_part = len(ids)
+    rows = [samples[s][0].n_rows for s in ids]
+    row0 = numpy.concatenate([[0], numpy.cumsum(rows)]).astype(numpy.int64)
+    ln0_h, p0_h = em.log_inits(numpy.stack([starts[s] for s in ids]))
+    ln0_d, p0_d = torch.from_numpy(ln0_h).to(dev), torch.from_numpy(p0_h).to(dev)
+    # the point estimate's contributor columns, one width for all samples (pad: column 0, masked on the host)
+    est = [[hap_index[con[1]] for con in finished[s]["contribs"]] for s in ids]
+    width = max([len(cols) for cols in est] + [1])
+    est_h = numpy.zeros((n_part, width), dtype=numpy.int64)
+    for j, cols in enumerate(est):
+        est_h[j, :len(cols)] = cols
+    est_d = torch.from_numpy(est_h).to(dev)
+    n_entries = n_part * n_boot
+    entry_bytes = [_detect_entry_bytes(rows[e // n_boot], n_haps, tile_rows, row_bytes) for e in range(n_entries)]
+    ld = DETECT_LD
+    out = {"cand": [], "ncand": [], "keep": [], "flag": [], "ln_cand": [], "ln_est": [], "state": [], "states": []}
+    var_count = getattr(args, "var_count", None)
+    for e0, e1 in _detect_chunks(entry_bytes, max_bytes):
+        count = e1 - e0
+        sample_of = numpy.arange(e0, e1) // n_boot                      # (index among the participating samples)
+        parts_off, parts_nd = [], []
+        for j in range(int(sample_of[0]), int(sample_of[-1]) + 1):
+            reps = int((sample_of == j).sum())
+            parts_off.append(samples[ids[j]][0].rec_off.repeat(reps))
+            parts_nd.append(samples[ids[j]][0].ndist.repeat(reps))
+        rows_h = numpy.array([rows[j] for j in sample_of], dtype=numpy.int64)
+        c_row0 = numpy.concatenate([[0], numpy.cumsum(rows_h)]).astype(numpy.int64)
+        j0, b0 = int(sample_of[0]), e0 - int(sample_of[0]) * n_boot
+        w0 = n_boot * int(row0[j0]) + b0 * rows[j0]                      # (wb's layout: the chunk's weights are one slice)
+        wts_c = wb[w0:w0 + int(c_row0[-1])]
+        off_c, nd_c = torch.cat(parts_off), torch.cat(parts_nd)
+        of_d = torch.from_numpy(sample_of).to(dev)
+        loop = em.SampleBatch(mat0.rec, off_c, nd_c, wts_c, c_row0, n_haps)
+        ln_cur, ln_new, state, states = loop.em_loop_device(ln0_d[of_d], p0_d[of_d], args.tolerance, args.max_iter)
+        vote = em.SampleFinish(mat0.rec, off_c, nd_c, wts_c, None, c_row0, n_haps)
+        votes, first, _ = vote.votes_device(ln_cur)
+        props = torch.exp(ln_new)
+        cand = torch.zeros((count, ld), dtype=torch.int32, device=dev)
+        ncand = torch.zeros(count, dtype=torch.int32, device=dev)
+        cprop = torch.zeros((count, ld), dtype=torch.float64, device=dev)
+        _lib.check(lib.mxm_detect_candidates(votes.data_ptr(), first.data_ptr(), rows_h.ctypes.data, props.data_ptr(),
+                                             state.data_ptr(), count, n_haps, float(args.min_reads), ld, cand.data_ptr(),
+                                             ncand.data_ptr(), cprop.data_ptr(), current_stream()), "mxm_detect_candidates")
+        keep = flag = None
+        if checked:
+            keep = torch.zeros((count, ld), dtype=torch.uint8, device=dev)
+            flag = torch.zeros(count, dtype=torch.int32, device=dev)
+            table_of = numpy.array([ids[j] for j in sample_of], dtype=numpy.int32)
+            _lib.check(lib.mxm_check_variants_entries(
+                obs.counts.data_ptr(), int(obs.counts.shape[0]), int(obs.L), var_tables.key_ptr.data_ptr(), var_tables.key.data_ptr(),
+                var_tables.n_haps, var_tables.site.data_ptr(), var_tables.site_key.data_ptr(), len(var_tables.site_h),
+                var_tables.max_pos, table_of.ctypes.data, count, cand.data_ptr(), ncand.data_ptr(), ld, float(args.min_var_reads),
+                float(args.frac_var_reads), float(args.var_fraction), 0 if var_count is None else 1,
+                0 if var_count is None else int(var_count), keep.data_ptr(), None, None, flag.data_ptr(), current_stream()),
+                "mxm_check_variants_entries")
+        # only E x 64 tables leave the device: the lists, and log theta_{k+1} at the lists and at the estimate's columns
+        slot_ok = torch.arange(ld, device=dev).reshape(1, ld) < ncand.clamp(0, ld).reshape(-1, 1)
+        at = torch.where(slot_ok, cand.to(torch.int64), torch.zeros_like(cand, dtype=torch.int64)).clamp(0, n_haps - 1)
+        out["ln_cand"].append(torch.gather(ln_new, 1, at).cpu().numpy())
+        out["ln_est"].append(torch.gather(ln_new, 1, est_d[of_d]))
+        out["state"].append(state)
+        out["cand"].append(cand.cpu().numpy())
+        out["ncand"].append(ncand.cpu().numpy())
+        out["keep"].append(keep.cpu().numpy().astype(bool) if checked else None)
+        out["flag"].append(flag.cpu().numpy() if checked else numpy.zeros(count, dtype=numpy.int32))
+        out["states"].extend(states)
+        del loop, vote, votes, first, props, ln_cur, ln_new
+
+    cand_h, ncand_h = numpy.concatenate(out["cand"]), numpy.concatenate(out["ncand"])
+    keep_h = numpy.concatenate(out["keep"]) if checked else None
+    flag_h, ln_cand = numpy.concatenate(out["flag"]), numpy.concatenate(out["ln_cand"])
+    ln_est_d = torch.cat(out["ln_est"])
+    ln_est = ln_est_d.cpu().numpy()
+    done_h = numpy.array([st[0] for st in out["states"]])
+    iters_h = numpy.array([st[1] for st in out["states"]])
+    # lo / hi / mean / sd through the bootstrap's summary entry, for the samples whose estimate has 1 .. 16 contributors
+    summary = {}
+    small = [j for j in range(n_part) if 1 <= len(est[j]) <= FINISH_KMAX]
+    if small:
+        s_ld = 4 if max(len(est[j]) for j in small) <= 4 else (8 if max(len(est[j]) for j in small) <= 8 else 16)
+        table = torch.full((len(small), n_boot, s_ld), -float("inf"), dtype=torch.float64, device=dev)
+        state_all = torch.cat(out["state"]).reshape(n_entries, -1)
+        for i, j in enumerate(small):
+            k = len(est[j])
+            table[i, :, :k] = ln_est_d[j * n_boot:(j + 1) * n_boot, :k]
+        st_small = torch.cat([state_all[j * n_boot:(j + 1) * n_boot] for j in small]).contiguous()
+        ncol = numpy.array([len(est[j]) for j in small], dtype=numpy.int32)
+        x = torch.zeros((len(small), n_boot, s_ld), dtype=torch.float64, device=dev)
+        four = torch.full((4, len(small), s_ld), float("nan"), dtype=torch.float64, device=dev)
+        sflag = torch.zeros(len(small), dtype=torch.int32, device=dev)
+        q_lo, q_hi = (1.0 - float(level)) / 2.0, (1.0 + float(level)) / 2.0
+        _lib.check(lib.mxm_bootstrap_summary(len(small), n_boot, s_ld, ncol.ctypes.data, table.data_ptr(), st_small.data_ptr(),
+                                             q_lo, q_hi, x.data_ptr(), four[0].data_ptr(), four[1].data_ptr(), four[2].data_ptr(),
+                                             four[3].data_ptr(), sflag.data_ptr(), current_stream()), "mxm_bootstrap_summary")
+        four_h = four.cpu().numpy()
+        for i, j in enumerate(small):
+            summary[j] = four_h[:, i, :len(est[j])].copy()
+    for j, s in enumerate(ids):
+        sl = slice(j * n_boot, (j + 1) * n_boot)
+        res = _detect_summary(cand_h[sl], ncand_h[sl], keep_h[sl] if checked else None, flag_h[sl], done_h[sl],
+                              finished[s]["contribs"], haplogroups, hap_index)
+        k = len(est[j])
+        props_boot = _exp_as_run_em_many(ln_est[sl, :k])
+        props_boot[done_h[sl] == 0] = numpy.nan
+        width_ok = numpy.arange(ld).reshape(1, ld) < numpy.clip(ncand_h[sl], 0, ld).reshape(-1, 1)
+        res.update({"columns": [con[1] for con in finished[s]["contribs"]], "props_boot": props_boot,
+                    "cand": cand_h[sl].copy(), "ncand": ncand_h[sl].copy(), "flag": flag_h[sl].copy(),
+                    "keep": keep_h[sl].copy() if checked else width_ok,
+                    "cand_props": numpy.where(width_ok, _exp_as_run_em_many(ln_cand[sl]), numpy.nan),
+                    "iters": iters_h[sl].copy(), "done": done_h[sl].copy(), "seed": seed, "level": level, "n_boot": n_boot,
+                    "var_check": "observed pileup" if checked else "off"})
+        if j in summary:
+            res.update({"lo": summary[j][0], "hi": summary[j][1], "mean": summary[j][2], "sd": summary[j][3],
+                        "summary": "mxm_bootstrap_summary"})
+        else:
+            res["summary"] = "omitted: %d contributors in the point estimate, the summary entry takes 1 .. %d" % (k, FINISH_KMAX)
+        detect[s] = res
+    return detect, skipped
+
+
+def detect(cm, wts, result_one, finished_one, haplogroups, args, **kwargs):
+    """detect_many for ONE sample: (its dict or None, the skip reason or None)."""
+    for key in ("inits", "sample_ids"):
+        if kwargs.get(key) is not None:
+            kwargs[key] = [kwargs[key]]
+    found, skipped = detect_many([(cm, wts)], [result_one], [finished_one], haplogroups, args, **kwargs)
+    return found[0], (skipped[0][1] if skipped else None)
+
+
 # ---- contributor support: nested-model fits over subsets of the reduced matrix (no counterpart in the reference) ---------------
 SUPPORT_MAX_FITS = 256              # MXM_SUPPORT_MAX_FITS of include/mixemt_hip_support.h: fits per sample (a cap: 2^8 - 1 subsets)
 SUPPORT_ALL_KMAX = 8                # models="all" enumerates 2^K - 1 subsets: refused above this many contributors

@@ -20,7 +20,8 @@ SRC = os.path.join(_PKG, "csrc", "mixemt_hip.hip")
 HDRS = [os.path.join(_ROOT, "include", name) for name in ("mixemt_hip.h", "mixemt_hip_tuning.h", "mixemt_hip_samples_finish.h",
                                                            "mixemt_hip_var_check.h", "mixemt_hip_assemble_samples.h",
                                                            "mixemt_hip_stats_samples.h", "mixemt_hip_samples_runs.h",
-                                                           "mixemt_hip_bootstrap.h", "mixemt_hip_support.h")]
+                                                           "mixemt_hip_bootstrap.h", "mixemt_hip_support.h",
+                                                           "mixemt_hip_detect.h")]
 LIB_DIR = os.path.join(_PKG, "lib")
 LIB = os.path.join(LIB_DIR, "libmixemt_hip.so")
 ARCH = "gfx950"

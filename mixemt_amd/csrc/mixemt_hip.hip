@@ -37,6 +37,7 @@
 //   aln_encode.hpp      HOST code: mxm_aln_encode, the batched alignment front end (process_reads + reduce_reads + row order)
 //   observe_kernels.hpp observe_bucket_kernel, observe_count_kernel (the pileup of the variant check: observe.py:56-86)
 //   var_check_kernels.hpp  check_variants_samples_kernel (the variant check of a cohort's samples: assemble.py:157-208)
+//   detect_kernels.hpp     the candidate rule and the variant check per (sample, replicate) entry, lists on the device
 //   assemble_kernels.hpp  consensus_kernel, new_variants_kernel, first_observed_kernel, extend_walk_kernel, extend_move_kernel
 //                       (consensus sequences and assembly extension over labelled pileups: assemble.py:431-585)
 //   assemble_samples_kernels.hpp  new_variants_samples_kernel, extend_walk_samples_kernel, extend_move_samples_kernel (a round
@@ -88,6 +89,7 @@
 #include "aln_walk.hpp"
 #include "observe_kernels.hpp"
 #include "var_check_kernels.hpp"
+#include "detect_kernels.hpp"
 #include "assemble_kernels.hpp"
 #include "assemble_samples_kernels.hpp"
 #include "stats_text_kernels.hpp"
@@ -3169,6 +3171,88 @@ extern "C" int mxm_check_variants_samples(const uint32_t *counts, int32_t S, int
         e = hipGetLastError();
     }
     const hipError_t ef = hipFreeAsync(tables, st);
+    HIP_TRY(e);
+    HIP_TRY(ef);
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// The detection bootstrap's tail (detect_kernels.hpp; include/mixemt_hip_detect.h): the candidate rule and the variant check
+// for entries whose tables are on the device.  Every refusal comes before the first HIP call; the one host table of each
+// entry is uploaded as mxm_check_variants_samples uploads its own.
+// ------------------------------------------------------------------------------------------
+static_assert(DETECT_MAX_LD == VCHK_MAX_LD, "the candidate rule fills the check's widest row");
+static bool detect_ld_ok(int32_t ld) { return ld == 4 || ld == 8 || ld == 16 || ld == 32 || ld == DETECT_MAX_LD; }
+
+extern "C" int mxm_detect_candidates(const double *votes, const int64_t *first, const int64_t *rows_host, const double *props,
+                                     const mxm_em_state *state, int32_t E, int32_t H, double min_reads, int32_t ld, int32_t *cand,
+                                     int32_t *ncand, double *cprop, void *stream) {
+    const char *who = "mxm_detect_candidates";
+    if (E < 0) return fail(-1, "%s: E < 0 (%d)", who, E);
+    if (H < 1) return fail(-1, "%s: H = %d: at least one haplogroup is needed", who, H);
+    if (!detect_ld_ok(ld)) return fail(-1, "%s: ld = %d: the candidate tables' row stride must be 4, 8, 16, 32 or 64", who, ld);
+    if (E == 0) return 0;
+    if (votes == nullptr || first == nullptr || rows_host == nullptr || props == nullptr || cand == nullptr || ncand == nullptr ||
+        cprop == nullptr)
+        return fail(-1, "%s: bad arguments (votes, first, rows_host, props, cand, ncand and cprop are required)", who);
+    for (int32_t e = 0; e < E; ++e)
+        if (rows_host[e] < 0) return fail(-1, "%s: entry %d has %lld rows", who, e, (long long)rows_host[e]);
+    hipStream_t st = (hipStream_t)stream;
+    static thread_local std::vector<int64_t> staged;      // (pageable and the call's own: read before the call returns)
+    staged.assign(rows_host, rows_host + (size_t)E);
+    int64_t *rows = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void **>(&rows), staged.size() * sizeof(int64_t), st));
+    hipError_t e = hipMemcpyAsync(rows, staged.data(), staged.size() * sizeof(int64_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(detect_candidates_kernel, dim3((unsigned)E), dim3(DETECT_THREADS), 0, st, votes, first, (const int64_t *)rows,
+                           props, state, (int)H, min_reads, (int)ld, cand, ncand, cprop);
+        e = hipGetLastError();
+    }
+    const hipError_t ef = hipFreeAsync(rows, st);
+    HIP_TRY(e);
+    HIP_TRY(ef);
+    return 0;
+}
+
+extern "C" int mxm_check_variants_entries(const uint32_t *counts, int32_t T, int64_t L, const int32_t *key_ptr, const int32_t *key,
+                                          int32_t H, const int32_t *site, const int32_t *site_key, int32_t n_sites, int64_t max_pos,
+                                          const int32_t *table_of_host, int32_t E, const int32_t *cand, const int32_t *ncand,
+                                          int32_t ld, double min_var_reads, double frac_var_reads, double var_fraction,
+                                          int32_t has_var_count, int32_t var_count, uint8_t *keep, int32_t *n_uniq, int32_t *n_found,
+                                          int32_t *flag, void *stream) {
+    const char *who = "mxm_check_variants_entries";
+    if (E < 0) return fail(-1, "%s: E < 0 (%d)", who, E);
+    if (!detect_ld_ok(ld)) return fail(-1, "%s: ld = %d: the candidate tables' row stride must be 4, 8, 16, 32 or 64", who, ld);
+    if (E == 0) return 0;
+    if (T < 1) return fail(-1, "%s: T = %d: at least one pileup table is needed", who, T);
+    if (table_of_host == nullptr || cand == nullptr || ncand == nullptr || flag == nullptr)
+        return fail(-1, "%s: bad arguments (table_of_host, cand, ncand and flag are required)", who);
+    for (int32_t e = 0; e < E; ++e)
+        if (table_of_host[e] < 0 || table_of_host[e] >= T)
+            return fail(-1, "%s: entry %d: table %d outside [0, %d)", who, e, table_of_host[e], T);
+    if (counts == nullptr || key_ptr == nullptr || key == nullptr || keep == nullptr || (n_sites > 0 && (site == nullptr || site_key == nullptr)))
+        return fail(-1, "%s: bad arguments (counts, key_ptr, key and keep are required, site and site_key with n_sites > 0)", who);
+    if ((reinterpret_cast<uintptr_t>(counts) & 15) != 0) return fail(-1, "%s: counts must be 16-byte aligned", who);
+    if (L <= 0 || n_sites < 0 || H < 1) return fail(-1, "%s: bad shape (L = %lld, n_sites = %d, H = %d)", who, (long long)L, n_sites, H);
+    if (max_pos >= L)
+        return fail(-1, "%s: max_pos = %lld: the tree's variants reach past the pileup (L = %lld)", who, (long long)max_pos, (long long)L);
+    if (L > VCHK_MAX_L)
+        return fail(-1, "%s: L = %lld: a sample's bitsets do not fit the kernel's LDS (L <= %d)", who, (long long)L, VCHK_MAX_L);
+    hipStream_t st = (hipStream_t)stream;
+    const size_t lds = vchk_lds_bytes(L);
+    RC_TRY(dynamic_lds_ok(reinterpret_cast<const void *>(&check_variants_entries_kernel), lds, "check_variants_entries_kernel"));
+    static thread_local std::vector<int32_t> staged;
+    staged.assign(table_of_host, table_of_host + (size_t)E);
+    int32_t *table_of = nullptr;
+    HIP_TRY(hipMallocAsync(reinterpret_cast<void **>(&table_of), staged.size() * sizeof(int32_t), st));
+    hipError_t e = hipMemcpyAsync(table_of, staged.data(), staged.size() * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    if (e == hipSuccess) {
+        hipLaunchKernelGGL(check_variants_entries_kernel, dim3((unsigned)E), dim3(VCHK_THREADS), lds, st, counts, L, key_ptr, key, (int)H,
+                           site, site_key, (int)n_sites, (const int32_t *)table_of, cand, ncand, (int)ld, min_var_reads, frac_var_reads,
+                           var_fraction, (int)(has_var_count != 0), (int)var_count, keep, n_uniq, n_found, flag);
+        e = hipGetLastError();
+    }
+    const hipError_t ef = hipFreeAsync(table_of, st);
     HIP_TRY(e);
     HIP_TRY(ef);
     return 0;

@@ -43,28 +43,23 @@ __device__ __forceinline__ bool vchk_found(const uint32_t *table, int32_t key, d
     return (double)seen >= threshold;
 }
 
-// counts [S][L][16]; key_ptr [H + 1] / key: every haplogroup's pos * 4 + code, distinct; site / site_key [n_sites]: the
-// tree's variant sites and site * 4 + code of the reference base there (-1: not one of ACGT); cand [S][ld] / ncand [S]:
-// the candidates in checking order.  A key outside [0, 4 L) (the entry's max_pos check rules it out) is counted as
-// unseen and touches nothing.
-__global__ __launch_bounds__(VCHK_THREADS) void check_variants_samples_kernel(
-    const uint32_t *__restrict__ counts, int64_t L, const int32_t *__restrict__ key_ptr, const int32_t *__restrict__ key,
-    const int32_t *__restrict__ site, const int32_t *__restrict__ site_key, int n_sites, const int32_t *__restrict__ cand,
-    const int32_t *__restrict__ ncand, int ld, double min_var_reads, double frac_var_reads, double var_fraction,
-    int has_var_count, int var_count, uint8_t *__restrict__ keep, int32_t *__restrict__ n_uniq, int32_t *__restrict__ n_found) {
-    extern __shared__ uint32_t vchk_lds[];
-    const int s = blockIdx.x, tid = threadIdx.x;
-    const int n = ncand[s];
-    if (n <= 0) return;
+// The check of ONE sample by its workgroup: table [L][16] its pileup, cand_row [n] its candidates in checking order (n > 0),
+// keep_row / uniq_row / found_row (the last two nullable) its rows of the outputs.  Shared by check_variants_samples_kernel and
+// check_variants_entries_kernel (detect_kernels.hpp): every thread of the workgroup calls it.
+__device__ __forceinline__ void vchk_check_sample(
+    uint32_t *vchk_lds, const uint32_t *__restrict__ table, int64_t L, const int32_t *__restrict__ key_ptr,
+    const int32_t *__restrict__ key, const int32_t *__restrict__ site, const int32_t *__restrict__ site_key, int n_sites,
+    const int32_t *__restrict__ cand_row, int n, double min_var_reads, double frac_var_reads, double var_fraction, int has_var_count,
+    int var_count, uint8_t *__restrict__ keep_row, int32_t *__restrict__ uniq_row, int32_t *__restrict__ found_row) {
+    const int tid = threadIdx.x;
     const int64_t uw = vchk_used_words(L), tw = vchk_touched_words(L);
     uint32_t *used = vchk_lds, *touched = used + uw, *tally = touched + tw;
     for (int64_t i = tid; i < uw + tw + 2; i += VCHK_THREADS) vchk_lds[i] = 0u;
     __syncthreads();
-    const uint32_t *table = counts + (int64_t)s * L * 16;
     const int32_t n_keys_max = (int32_t)(L < (1 << 29) ? 4 * L : 0x7fffffff);
 
     for (int c = 0; c < n; ++c) {
-        const int h = cand[(int64_t)s * ld + c];
+        const int h = cand_row[c];
         const int32_t k0 = key_ptr[h], k1 = key_ptr[h + 1];
         // ---- the candidate's keys that nobody has claimed, and those of them the sample shows ----
         int uniq = 0, found = 0;
@@ -85,9 +80,9 @@ __global__ __launch_bounds__(VCHK_THREADS) void check_variants_samples_kernel(
         if (tid == 0) {
             tally[0] = 0u;
             tally[1] = 0u;
-            keep[(int64_t)s * ld + c] = kept ? 1 : 0;
-            if (n_uniq != nullptr) n_uniq[(int64_t)s * ld + c] = nu;
-            if (n_found != nullptr) n_found[(int64_t)s * ld + c] = nf;
+            keep_row[c] = kept ? 1 : 0;
+            if (uniq_row != nullptr) uniq_row[c] = nu;
+            if (found_row != nullptr) found_row[c] = nf;
         }
         if (kept) {                                                   // (uniform: a dropped candidate claims nothing)
             // ---- its found keys are claimed; every position it has a variant on is touched ----
@@ -114,6 +109,25 @@ __global__ __launch_bounds__(VCHK_THREADS) void check_variants_samples_kernel(
         }
         __syncthreads();
     }
+}
+
+// counts [S][L][16]; key_ptr [H + 1] / key: every haplogroup's pos * 4 + code, distinct; site / site_key [n_sites]: the
+// tree's variant sites and site * 4 + code of the reference base there (-1: not one of ACGT); cand [S][ld] / ncand [S]:
+// the candidates in checking order.  A key outside [0, 4 L) (the entry's max_pos check rules it out) is counted as
+// unseen and touches nothing.
+__global__ __launch_bounds__(VCHK_THREADS) void check_variants_samples_kernel(
+    const uint32_t *__restrict__ counts, int64_t L, const int32_t *__restrict__ key_ptr, const int32_t *__restrict__ key,
+    const int32_t *__restrict__ site, const int32_t *__restrict__ site_key, int n_sites, const int32_t *__restrict__ cand,
+    const int32_t *__restrict__ ncand, int ld, double min_var_reads, double frac_var_reads, double var_fraction,
+    int has_var_count, int var_count, uint8_t *__restrict__ keep, int32_t *__restrict__ n_uniq, int32_t *__restrict__ n_found) {
+    extern __shared__ uint32_t vchk_lds[];
+    const int s = blockIdx.x;
+    const int n = ncand[s];
+    if (n <= 0) return;
+    const int64_t at = (int64_t)s * ld;
+    vchk_check_sample(vchk_lds, counts + (int64_t)s * L * 16, L, key_ptr, key, site, site_key, n_sites, cand + at, n, min_var_reads,
+                      frac_var_reads, var_fraction, has_var_count, var_count, keep + at, n_uniq != nullptr ? n_uniq + at : nullptr,
+                      n_found != nullptr ? n_found + at : nullptr);
 }
 
 #endif  // MIXEMT_VAR_CHECK_KERNELS_HPP

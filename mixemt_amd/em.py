@@ -824,6 +824,24 @@ class SampleBatch(object):
                                                 host_state), "mxm_em_loop_samples")
         return ln_cur, ln_new, [(s.done, s.iters, s.l1) for s in host_state]
 
+    def em_loop_device(self, ln0, p0, tolerance, max_iter, check_every=16):
+        """em_loop from a start that is on the device already: ln0 / p0 [S][H] as log_inits forms them (both are taken
+        over and updated in place).  Returns (ln_cur, ln_new, the states ON THE DEVICE, [(done, iters, l1)]); nothing
+        H-sized crosses the bus (assign.detect_many's entries share a few starts)."""
+        if tuple(ln0.shape) != (self.n_entries, self.n_haps) or tuple(p0.shape) != (self.n_entries, self.n_haps):
+            raise ValueError("the start must be [%d][%d]" % (self.n_entries, self.n_haps))
+        props_cur, ln_cur = p0.contiguous(), ln0.contiguous()
+        ln_new = ln_cur.clone()
+        colsum = torch.zeros_like(props_cur)
+        state = new_state(self.n_entries, self.dev)
+        host_state = (_lib.EmState * self.n_entries)()
+        _lib.check(self.lib.mxm_em_loop_samples(ctypes.byref(self.coded), self.row0_ptr, self.n_entries, self.wts.data_ptr(),
+                                                self.n_haps, props_cur.data_ptr(), ln_cur.data_ptr(), ln_new.data_ptr(),
+                                                colsum.data_ptr(), state.data_ptr(), float(tolerance), int(max_iter),
+                                                int(check_every), self.ws.data_ptr(), self.ws_bytes, current_stream(),
+                                                host_state), "mxm_em_loop_samples")
+        return ln_cur, ln_new, state, [(s.done, s.iters, s.l1) for s in host_state]
+
 
 class SampleFinish(object):
     """
@@ -890,6 +908,24 @@ class SampleFinish(object):
         errors = [st.error != 0 for st in (_lib.EmState * n).from_buffer_copy(raw)]
         table_h = table.cpu().numpy()
         return best, votes.cpu().numpy(), table_h[0], table_h[1], lse, errors
+
+    def votes_device(self, ln_props):
+        """votes() for ln_props [S][H] that is on the device, with NOTHING downloaded: returns (votes [S][H] double, first
+        [S][H] int64, the vote's states [S]) as device tensors (mxm_votes_samples; no counts, no row normaliser).  A sample
+        with a row that has no usable record has NaN votes and state.error = 1."""
+        n, n_haps = self.n_entries, self.n_haps
+        if tuple(ln_props.shape) != (n, n_haps) or ln_props.dtype != torch.float64:
+            raise ValueError("ln_props must be a float64 [%d][%d] device tensor" % (n, n_haps))
+        lnp = ln_props.contiguous()
+        best = torch.empty(self.n_rows, dtype=torch.int32, device=self.dev)
+        votes = torch.empty((n, n_haps), dtype=torch.float64, device=self.dev)
+        first = torch.empty((n, n_haps), dtype=torch.int64, device=self.dev)
+        state = new_state(n, self.dev)
+        _lib.check(self.lib.mxm_votes_samples(ctypes.byref(self.coded), self.row0_ptr, n, n_haps, self.wts.data_ptr(),
+                                              lnp.data_ptr(), None, None, best.data_ptr(), votes.data_ptr(), None,
+                                              first.data_ptr(), None, state.data_ptr(), self.ws.data_ptr(), self.ws_bytes,
+                                              current_stream()), "mxm_votes_samples")
+        return votes, first, state
 
     def gather(self, cols, ncol, ld):
         """out[r][i] = M[r][cols[s][i]] (i < ncol[s]; -inf in the pad columns): [R][ld] on the device."""

@@ -243,6 +243,49 @@ def report_support_many(out, finished, support, titles=None):
             out.write("best_bic\t%s\t%.4f\n" % (",".join(best["names"]), best["bic"]))
 
 
+DETECTION_HEADER = ("# detection bootstrap: call frequencies under resampled reads, conditional on the OBSERVED pileup (the variant "
+                    "check is not resampled) and on the EM's stop rule; not the frequencies of the full pipeline\n")
+
+
+def report_detection_many(out, finished, detect, titles=None):
+    """
+    The detection bootstrap of a cohort (assign.detect_many's list `detect` beside finish_many's `finished`).  The first
+    line says what the frequencies are conditional on; then one block per sample: '# title' (with titles), a line
+    '# n_used / n_boot replicates used; variant check: ...', a table with the columns haplogroup, candidate, kept, freq
+    (kept / n_used, '%.4f'; NA without a usable replicate), estimate (the point estimate's proportion, '%.4f', or '-'),
+    every column right-aligned to its widest cell, then 'same_set<TAB>count', 'set_size<TAB>size<TAB>count' lines and
+    'set<TAB>name,name,...<TAB>count' for the most frequent kept sets ('-' for the empty set), then
+    'failed<TAB>reason<TAB>count' lines.  A skipped sample (detect[s] is None) gets '# skipped: no detection bootstrap'.
+    """
+    n = len(finished)
+    if len(detect) != n or (titles is not None and len(titles) != n):
+        raise ValueError("report_detection_many: one detection result (and one title) per sample is needed")
+    out.write(DETECTION_HEADER)
+    for s in range(n):
+        if titles is not None:
+            out.write("# %s\n" % (titles[s],))
+        res = detect[s]
+        if res is None:
+            out.write("# skipped: no detection bootstrap\n")
+            continue
+        n_used = res["n_used"]
+        out.write("# %d / %d replicates used; variant check: %s\n" % (n_used, res["n_boot"], res["var_check"]))
+        cells = [["haplogroup", "candidate", "kept", "freq", "estimate"]]
+        for name, n_cand, n_kept, _, prop in res["detection"]:
+            cells.append([str(name), "%d" % n_cand, "%d" % n_kept, "%.4f" % (n_kept / float(n_used)) if n_used else "NA",
+                          "-" if prop is None else "%.4f" % prop])
+        widths = [max(len(row[i]) for row in cells) for i in range(5)]
+        for row in cells:
+            out.write("  ".join(cell.rjust(w) for cell, w in zip(row, widths)) + "\n")
+        out.write("same_set\t%d\n" % res["same_set"])
+        for size, count in res["set_sizes"].items():
+            out.write("set_size\t%d\t%d\n" % (size, count))
+        for names, count in res["sets"]:
+            out.write("set\t%s\t%d\n" % (",".join(names) if names else "-", count))
+        for why, count in res["n_failed"].items():
+            out.write("failed\t%s\t%d\n" % (why, count))
+
+
 def _stats_block_plan(contribs_list, cohort):
     """
     The obs.tab blocks of every sample, host only: per sample None (no contributors: the reference has no threshold and
