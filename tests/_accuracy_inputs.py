@@ -15,7 +15,10 @@ where kernels go wrong.  Everything comes from oracle/, mixemt_amd.synth and num
     the kernels take any positive vector, and so does the reference;
   * the LOOP tests (tests/test_exact_traj.py, tests/test_gpu_accuracy_loops.py): 96-row matrices (loop_matrix) and a third
     vector, "deep" (deep_vector): ln p ~ U(-760, -690) around the skewed vector's three entries, i.e. proportions that are
-    subnormal or zero in linear space.
+    subnormal or zero in linear space;
+  * the INSTANCE sweep (tests/test_gpu_instances.py, tests/test_exact_ref.py): at most 64 rows of any width in [65, 8192]
+    (edge_rows: column slices of the full-width real rows, few_values beyond Build 17), and few_quads, few_values with every
+    value four columns long, for the quad passes beyond Build 17's width.
 """
 import numpy
 
@@ -69,6 +72,28 @@ def few_values(n_rows, n_haps):
         mat.setflags(write=False)
         _matrices[key] = mat
     return _matrices[key]
+
+
+def edge_rows(b17, n_haps, n_rows):
+    """(label, log matrix [n_rows][n_haps]) of the instance sweep (tests/test_gpu_instances.py, at most 64 rows of ANY
+    width): up to Build 17's width the first n_haps columns of real_rows(b17, 5408, ...) -- the sub-tree of the first
+    n_haps haplogroups, whose matrix over the same reads is this column slice bit for bit (the variant sites are the
+    whole tree's either way) -- from 37 rows on the last four of them merged pairs (rows of several hundred distinct
+    values: wide records at full width); beyond it few_values.  Column 0 stays the reads' contributor."""
+    if n_haps > 5408 or n_haps < 65:
+        return "few values[:%d] %d" % (n_rows, n_haps), numpy.array(few_values(64, n_haps)[:n_rows])
+    n_pairs = 4 if n_rows >= 37 else 0
+    rows = [real_rows(b17, 5408, "reads")[:n_rows - n_pairs, :n_haps]]
+    if n_pairs:
+        rows.append(real_rows(b17, 5408, "pairs")[:n_pairs, :n_haps])
+    return "reads + pairs[:%d] %d" % (n_rows, n_haps), numpy.ascontiguousarray(numpy.concatenate(rows))
+
+
+def few_quads(n_rows, n_haps):
+    """few_values with every value four columns long: at most 40 distinct aligned quads per row -- every row of it
+    gets a quad record, which few_values' rows (40^4 possible quads) never do.  The quad passes beyond Build 17's width."""
+    quarter = few_values(n_rows, (n_haps + 3) // 4)
+    return numpy.ascontiguousarray(numpy.repeat(quarter, 4, axis=1)[:, :n_haps])
 
 
 def weights(n_rows, seed=0):

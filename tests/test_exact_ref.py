@@ -61,3 +61,44 @@ def test_three_mutants_are_outside_the_tight_bound(cases):
         assert rel_b > bound, label
         if not label.startswith("few values"):             # on real rows PROPS_ATOL = 1e-9 cannot see it (a random matrix is not
             assert shift < 1e-9, label                     # explained by the skewed vector: there the proportions move visibly)
+
+
+# ---------------------------------------------------------------- the instance sweep's rule (tests/test_gpu_instances.py)
+def _edge_pass(lin, props, wts, drop_last=False, pad=None):
+    """A sequential fp64 pass as a kernel with a wrong predicate on its last chunk would run it (the mutant pattern of
+    tests/_exact_traj.py): drop_last = the class's last column is never visited (not in Z, its sum stays 0); pad = the
+    value of ONE pad column behind the row that the pass reads as if it were a column (its proportion: the last one's)."""
+    n_haps = lin.shape[1]
+    if drop_last:
+        out = numpy.zeros(n_haps)
+        out[:-1] = _exact.seq_colsum(lin[:, :-1], props[:-1], wts)
+        return out
+    wide = numpy.concatenate([lin, numpy.full((len(lin), 1), pad)], axis=1)
+    with numpy.errstate(invalid="ignore"):
+        return _exact.seq_colsum(wide, numpy.append(props, props[-1]), wts)[:n_haps]
+
+
+def test_edge_mutants_fail_the_rule_at_every_edge_width(b17):
+    """At every (edge width, row count) at which tests/test_gpu_instances.py checks a colsum (_instances.colsum_shapes),
+    on edge_rows of that shape: the honest sequential pass is inside both bounds; a pass that drops the last column, and one
+    that reads one pad column too many (the pad holds NaN), are outside the tight bound -- under both proportion vectors,
+    the skewed one (p_last = 1e-12) included."""
+    import _instances as inst
+    shapes = inst.colsum_shapes()
+    assert shapes[0][0] == 65 and shapes[-1][0] == 8192 and set(r for _, r in shapes) == {3, 37, 64}
+    assert set(w for w, _ in shapes) >= set(w for w in inst.edge_widths(inst.COLSUM_SITES))
+    for n_haps, n_rows in shapes:
+        label, mat = inputs.edge_rows(b17, n_haps, n_rows)
+        wts = inputs.weights(n_rows)
+        lin = inputs.linearise(mat)
+        for vec, (props, _) in inputs.prop_vectors(n_haps).items():
+            _exact.check_products(lin, props)
+            exact = _exact.exact_colsum(lin, props, wts)
+            rel_seq = _exact.rel_err(_exact.seq_colsum(lin, props, wts), exact)
+            bound = _exact.tight_bound(rel_seq)
+            assert rel_seq <= _exact.derived_bound(n_rows, n_haps), (label, vec)
+            rel_drop = _exact.rel_err(_edge_pass(lin, props, wts, drop_last=True), exact)
+            rel_pad = _exact.rel_err(_edge_pass(lin, props, wts, pad=numpy.nan), exact)
+            assert rel_drop > bound and rel_pad > bound, (label, vec, rel_drop, rel_pad, bound)
+        print("%-34s R=%-2d rel(T_seq) = %.1f u, bound %.1f u: last column dropped %.3g, NaN pad read %.3g"
+              % (label, n_rows, rel_seq / _exact.U, bound / _exact.U, rel_drop, rel_pad))

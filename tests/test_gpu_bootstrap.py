@@ -101,6 +101,30 @@ def test_a_sample_keeps_its_draws_alone_last_in_a_batch_and_under_another_b():
     assert not _same_bits(_slices(alone, wb, 8)[0], first)                  # the id is in the counter
 
 
+@pytest.mark.parametrize("n_boot", [65, 130])
+def test_global_counters_in_a_later_chunk_of_replicates(n_boot):
+    """A sample beyond MXM_BOOTSTRAP_LDS_ROWS draws its replicates in launches of BOOT_CHUNK = 64 (bootstrap_kernels.hpp),
+    from the second launch on with b0 > 0: 65 replicates = a second launch of one, 130 = two full launches and one of two.
+    The batch holds a sample one past the limit, one at it and a small one; every replicate of every sample bit for bit."""
+    cases = _weight_cases()
+    names, ids = ("one past the limit", "at the limit", "zero ends"), (70000, 2 ** 32 - 1, 9)
+    assert [len(cases[n]) for n in names] == [LDS_ROWS + 1, LDS_ROWS, 257]
+    fin = _finish([cases[n] for n in names])
+    wb, errors = fin.boot_weights(n_boot, SEED, ids)
+    assert errors == [0, 0, 0]
+    got_all = _slices(fin, wb, n_boot)
+    wb64, errors = fin.boot_weights(64, SEED, ids)
+    assert errors == [0, 0, 0]
+    for name, s_id, got, first in zip(names, ids, got_all, _slices(fin, wb64, 64)):
+        w = cases[name]
+        assert got.shape == (n_boot, len(w))
+        assert (got.sum(axis=1) == w.sum()).all(), name                     # every replicate's counts sum to N_s exactly
+        assert not got[:, w == 0].any(), name
+        assert _same_bits(got, ref.resample_all(w, SEED, s_id, n_boot)), name
+        assert _same_bits(got[:64], first), name                            # the first chunk is the B = 64 call's
+        assert len({tuple(r) for r in got}) == n_boot, name                 # no replicate of a later chunk repeats an earlier one
+
+
 def test_a_refused_sample_is_flagged_and_leaves_its_neighbours_intact():
     cases = _weight_cases()
     for bad, code in ((numpy.array([1.0, 2.5, 3.0]), 1), (numpy.array([1.0, -2.0, 3.0]), 1), (numpy.array([1.0, numpy.nan]), 1),

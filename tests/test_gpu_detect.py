@@ -17,7 +17,7 @@ from conftest import ROOT
 
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 import _detect_ref as ref  # noqa: E402
-from test_gpu_var_check import TOY, TOY_CASES, cohort, host_check, table  # noqa: E402,F401
+from test_gpu_var_check import G, T, TOY, TOY_CASES, cohort, end_cases, end_tree, host_check, long_reference_lengths, table  # noqa: E402,F401
 from test_observe import asm_args  # noqa: E402
 from test_samples_finish_host import finish_args  # noqa: E402
 from test_var_check_host import toy_tree  # noqa: E402
@@ -293,6 +293,35 @@ def test_toy_tree_edges_through_the_entries_call():
     for e, c in enumerate(plain):
         got = [(bool(keep[e, i]), int(uniq[e, i]), int(found[e, i])) for i in range(len(c[2]))]
         assert flag[e] == 0 and got == host_check(phy, tables[e], c[2], args), c[0]
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["the cap", "just above 64 KiB"])
+def test_entries_call_with_more_than_64k_of_lds(which):
+    """check_variants_entries_kernel on the opt-in path (tests/test_gpu_var_check.py, section 7): the toy tree with variant
+    sites and candidates' variants at the last two positions of a reference of L bases; three entries, each its own table."""
+    from mixemt_amd import assign
+    L = long_reference_lengths()[which]
+    phy = end_tree(L)
+    tab = assign.VarCheckTables.build(phy, TOY, "cuda")
+    index = {h: i for i, h in enumerate(TOY)}
+    cases = [c for c in end_cases(L) if not c[3]] + [("one", {(0, G): 9, (2, T): 9, (4, T): 9, (L - 2, T): 9, (L - 1, T + 7): 9}, ["B", "D", "H"], {})]
+    assert len(cases) == 3
+    args = asm_args()
+    tables = numpy.stack([table(L, c[1]) for c in cases])
+    rows, ncand = lists_to_rows([[index[n] for n in c[2]] for c in cases], 4)
+    keep, uniq, found, flag = entries_check(tables, tab, rows, ncand, [0, 1, 2], args, 4)
+    for e, c in enumerate(cases):
+        got = [(bool(keep[e, i]), int(uniq[e, i]), int(found[e, i])) for i in range(len(c[2]))]
+        assert flag[e] == 0 and got == host_check(phy, tables[e], c[2], args), (L, c[0])
+        assert is_sentinel(keep[e, len(c[2]):])
+    # ... and the argument-carrying cases one entry at a time
+    for what, cells, names, kw in end_cases(L):
+        if kw:
+            tbl = table(L, cells)
+            rows, ncand = lists_to_rows([[index[n] for n in names]], 4)
+            keep, uniq, found, flag = entries_check(tbl[None], tab, rows, ncand, [0], asm_args(**kw), 4)
+            got = [(bool(keep[0, i]), int(uniq[0, i]), int(found[0, i])) for i in range(len(names))]
+            assert flag[0] == 0 and got == host_check(phy, tbl, names, asm_args(**kw)), (L, what)
 
 
 # ---- 3. end to end ----------------------------------------------------------------------------------------------------

@@ -283,3 +283,63 @@ def test_finish_many_batch_route_samples_take_the_device_check(b17):
     # the check off: neither route is named
     plain = assign.finish_many(samples, results, haps, finish_args(var_check=False), obs=pileup)
     assert [r["var_check"] for r in plain] == [None] * 3
+
+
+# ---- 7. dynamic LDS above 64 KiB: the bitsets' last words ----------------------------------------------------------------------
+def lds_bytes(L):
+    """vchk_lds_bytes (csrc/var_check_kernels.hpp), restated: the `used` bitset over 4 L keys, `touched` over L positions,
+    two tally words."""
+    return ((4 * L + 31) // 32 + (L + 31) // 32 + 2) * 4
+
+
+def long_reference_lengths():
+    """(the cap MXM_VAR_CHECK_MAX_L, the first L whose workgroup needs more than 64 KiB): both run the opt-in path."""
+    with open(os.path.join(ROOT, "include", "mixemt_hip_var_check.h")) as src:
+        cap = int(re.search(r"#define\s+MXM_VAR_CHECK_MAX_L\s+(\d+)", src.read()).group(1))
+    first = next(L for L in range(1, cap + 1) if lds_bytes(L) > 64 * 1024)
+    assert lds_bytes(first - 1) <= 64 * 1024 < lds_bytes(first) < lds_bytes(cap) and first < cap
+    return cap, first
+
+
+def end_tree(L):
+    """The toy tree with its last two variant positions (B's A8T, D's A9T) moved to the LAST two positions of a reference
+    of L bases: two variant sites and two candidates' variants in the last word of both bitsets."""
+    from mixemt_amd import phylotree
+    rows = [r.replace("A8T", "A%dT" % (L - 1)).replace("A9T", "A%dT" % L) for r in phylotree.example_rows()]
+    phy = phylotree.Phylotree(rows)
+    phy.refseq = "A" * L
+    assert sorted(phy.get_variant_pos())[-2:] == [L - 2, L - 1]
+    return phy
+
+
+def end_cases(L):
+    """(what, cells, candidates, args) at the end of the reference; the expected triples are the host check's."""
+    e1, e2 = L - 1, L - 2
+    return [("the last position found", {(e1, T): 5}, ["D"], {"var_count": 1}),
+            ("the last position missing", {(2, T): 5, (4, T): 5, (6, T): 5}, ["D"], {"var_fraction": 0.8}),
+            ("both last positions, the shared ones claimed first", {(0, G): 5, (2, T): 5, (4, T): 5, (e2, T): 5, (e1, T): 5}, ["H", "B", "D"], {}),
+            ("the last two sites claimed as ancestral", {(0, G): 5, (e2, A): 50, (e1, A + 7): 50}, ["I", "B", "D"], {}),
+            ("seen == min_var_reads on the last row of the table", {(e1, T): 2, (e1, T + 7): 1, (e2, T + 7): 3}, ["D", "B"], {"var_count": 1})]
+
+
+@pytest.mark.parametrize("which", [0, 1], ids=["the cap", "just above 64 KiB"])
+def test_toy_tree_with_more_than_64k_of_lds(which):
+    from mixemt_amd import assign
+    L = long_reference_lengths()[which]
+    phy = end_tree(L)
+    tab = assign.VarCheckTables.build(phy, TOY, "cuda")
+    assert tab.max_pos == L - 1
+    index = {h: i for i, h in enumerate(TOY)}
+    cases = [c[:4] for c in TOY_CASES if not ({"B", "D"} & set(c[2]))] + end_cases(L)
+    for what, cells, names, kw in cases:
+        args = asm_args(**kw)
+        tbl = table(L, cells)
+        got = device_check(tbl[None], tab, index, [names], args)[0]
+        assert got == host_check(phy, tbl, names, args), (L, what)
+    assert device_check(table(L, {(L - 1, T): 5})[None], tab, index, [["D"]], asm_args(var_count=1))[0] == [(True, 5, 1)]
+    # S = 3, every sample its own table (8 MiB each at the cap) and its own number of candidates
+    args = asm_args()
+    picked = [end_cases(L)[2], end_cases(L)[3], ("one", {(L - 2, T): 9}, ["B"], {})]
+    tables = [table(L, c[1]) for c in picked]
+    got = device_check(numpy.stack(tables), tab, index, [c[2] for c in picked], args)
+    assert got == [host_check(phy, t, c[2], args) for t, c in zip(tables, picked)]

@@ -1,14 +1,20 @@
 #!/usr/bin/env python
 """
-profiles/accuracy/README.md from a run of tests/test_gpu_accuracy.py, tests/test_gpu_accuracy_loops.py and
-tests/test_gpu_accuracy_consumers.py on the GPU: the modules write the figures they measured -- one pass per form (the
+profiles/accuracy/README.md from a run of tests/test_gpu_accuracy.py, tests/test_gpu_accuracy_loops.py,
+tests/test_gpu_accuracy_consumers.py and tests/test_gpu_instances.py on the GPU: the modules write the figures they measured -- one pass per form (the
 kernel's error against the extended-precision reference, the sequential fp64 pass's, their ratio, the loops' ln_new error),
 every loop form over K = 2, 3, 10 and 40 iterations (the error of ln_new in units of K u max(1, max |ln|), beside the
 comparison pass's), and every consumer of the posterior (error, the comparison pass's, the bound, undecided rows) -- as
 tables; this wraps them with the text that explains the columns.
     python tools/accuracy_report.py [output.md [more pytest arguments]]
     python tools/accuracy_report.py --from-tables PREFIX [output.md]     the tables a run with MXM_ACCURACY_REPORT=PREFIX
-                                                                         left (PREFIX, PREFIX.loops, PREFIX.consumers)
+                                                                         left (PREFIX, PREFIX.loops, PREFIX.consumers,
+                                                                         PREFIX.instances)
+    python tools/accuracy_report.py --instances PREFIX [output.md]       only the section "Every instance at its edges" of an
+                                                                         existing report, from PREFIX.instances (a run of
+                                                                         tests/test_gpu_instances.py alone)
+    ... --note "TEXT"    (any form) a paragraph in front of that section's tables: what the run cost -- the wall time of the GPU
+                         suite with and without the module, which no test measures
 """
 import os
 import subprocess
@@ -53,27 +59,66 @@ exact answer.  "orphans below t" are rows supported only by columns with `ln p <
 assertion is the line of the whole matrix).
 
 """
+INSTANCES = """
+# Every instance at its edges
+
+`tests/test_gpu_instances.py`: every kernel instance the width dispatchers of `mixemt_hip.hip` compile
+(`tests/_instances.py` restates each site's formula from the width to the instance), run at the first and at the last width
+that reach it -- one call per case on 3, 37 or 64 rows, under the rule of the entry's own tests: `colsum` under the two
+bounds above; `exp` in ulp for `mxm_linearize`; absolute errors of posterior and `ln_new` for `mxm_em_step` and the
+one-launch loops (three iterations); exact labels and votes for the argmax entries; the encoder's round trip and the
+builders bit for bit ("other" then says what the case measured).
+
+"""
+
+
+NOTE = [""]
 
 
 def write_report(out, parts):
     with open(out, "w") as dst:
-        for head, part in zip((HEAD, LOOPS, CONSUMERS), parts):
+        for head, part in zip((HEAD, LOOPS, CONSUMERS, INSTANCES), parts):
+            if head is INSTANCES and not os.path.exists(part):       # (a run without tests/test_gpu_instances.py)
+                continue
+            dst.write(head + (NOTE[0] if head is INSTANCES else ""))
             with open(part) as src:
-                dst.write(head + src.read())
+                dst.write(src.read())
+
+
+def replace_instances(out, table):
+    """The section "Every instance at its edges" of an existing report: replaced, or appended."""
+    with open(out) as src:
+        text = src.read()
+    at = text.find(INSTANCES.lstrip("\n").split("\n")[0])
+    if at >= 0:
+        text = text[:at].rstrip("\n") + "\n"
+    with open(table) as src:
+        text += INSTANCES + NOTE[0] + src.read()
+    with open(out, "w") as dst:
+        dst.write(text)
 
 
 def main():
+    if "--note" in sys.argv:
+        at = sys.argv.index("--note")
+        NOTE[0] = sys.argv[at + 1].strip() + "\n\n"
+        del sys.argv[at:at + 2]
     if len(sys.argv) > 2 and sys.argv[1] == "--from-tables":
         out = os.path.abspath(sys.argv[3]) if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "accuracy", "README.md")
-        write_report(out, [sys.argv[2], sys.argv[2] + ".loops", sys.argv[2] + ".consumers"])
+        write_report(out, [sys.argv[2], sys.argv[2] + ".loops", sys.argv[2] + ".consumers", sys.argv[2] + ".instances"])
+        return 0
+    if len(sys.argv) > 2 and sys.argv[1] == "--instances":
+        out = os.path.abspath(sys.argv[3]) if len(sys.argv) > 3 else os.path.join(ROOT, "profiles", "accuracy", "README.md")
+        replace_instances(out, sys.argv[2] + ".instances")
         return 0
     out = os.path.abspath(sys.argv[1]) if len(sys.argv) > 1 else os.path.join(ROOT, "profiles", "accuracy", "README.md")
     table = out + ".table"
     env = dict(os.environ, MXM_ACCURACY_REPORT=table)
     rc = subprocess.call([sys.executable, "-m", "pytest", "-m", "gpu", "-q", os.path.join(ROOT, "tests", "test_gpu_accuracy.py"),
                           os.path.join(ROOT, "tests", "test_gpu_accuracy_loops.py"),
-                          os.path.join(ROOT, "tests", "test_gpu_accuracy_consumers.py")] + sys.argv[2:], cwd=ROOT, env=env)
-    parts = [table, table + ".loops", table + ".consumers"]
+                          os.path.join(ROOT, "tests", "test_gpu_accuracy_consumers.py"),
+                          os.path.join(ROOT, "tests", "test_gpu_instances.py")] + sys.argv[2:], cwd=ROOT, env=env)
+    parts = [table, table + ".loops", table + ".consumers", table + ".instances"]
     if all(os.path.exists(p) for p in parts) and rc == 0:          # (a failed or interrupted run leaves the committed tables alone)
         write_report(out, parts)
     for part in parts:
